@@ -27,14 +27,22 @@ main.cpp:379-385): per frame, on the frame's lane stream, the render, the librar
 From N = 4 rank 0 is a compositor (--compositor): it renders no band and assembles every frame,
 while ranks 1..N-1 split the frame (tiles.split_band_spec). A K-way band renders K frames per
 launch (8 from K = 7; vrt_render_temporal_batch_async).
-The JSON's "render_only" object times the same frames without the gather (labelled; --no-gather
+With --full the JSON's "render_only" object times the same frames without the gather (--no-gather
 makes that the timed path and gathers the last frame once instead). Default --scaling strong: the
 config's frame (C3: 1920x1080) is split N ways, the reference's one frame per draw
 (main.cpp:325-361) tiled across the GPUs; --scaling weak renders an N-fold taller frame of the same
 view instead (each rank a config-sized band; opt-in, no BASELINE config names that frame).
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config C1|C2|C3|C4]
+A plain run does what the headline figure needs: set-up (with one counted launch per part for the
+rays per frame), warm-up, the K timed frames, --dump-outputs, the JSON line. --full adds the
+passes after the timed region: the check of the timed path against the exact instance (and the
+oracle), the CPU baseline, the launch-timing, exchange-timing and latency passes, the render-only
+timing of gathered frames (and with them the roofline's per-launch fields); their JSON fields are
+null without it.
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config C1|C2|C3|C4] [--full]
                        [--output rgba8|f32] [--alpha A] [--scaling strong|weak] [--lanes L]
+                       [--dump-outputs DIR]
 """
 import argparse
 import faulthandler
@@ -71,6 +79,17 @@ def parse():
     ap.add_argument("--steps", type=int, default=500)
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--config", default="C3", choices=sorted(CONFIGS))
+    ap.add_argument("--full", action="store_true",
+                    help="also run the passes after the timed region: the check of the timed path "
+                         "(--verify-frames, --oracle-check), the CPU baseline (--cpu-seconds), the "
+                         "launch-timing, exchange-timing and latency passes, the render-only timing "
+                         "of gathered frames and the roofline's per-launch fields; without it those "
+                         "JSON fields are null")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed frame's call returned (this rank's band buffer, "
+                         "on rank 0 of a gathered run the assembled frame) to DIR/frame.npy as "
+                         "float32 (RGBA8 bytes as 0..255), a fixed seeded sample of its pixels when "
+                         "larger than 64 MB (dump_outputs)")
     ap.add_argument("--device-warmup-ms", type=float, default=200.0,
                     help="untimed frames for this long before the W warmup frames: the engine "
                          "clock's DPM ramp under this load (~1.9 -> ~2.3 GHz over the first "
@@ -239,6 +258,24 @@ def cpu_baseline(cam, vox, n, params, budget_s, threads):
                        f"{dt:.1f} s"), frame
 
 
+DUMP_LIMIT_BYTES = 60_000_000   # per run (--dump-outputs): below 64 MB with the .npy header
+
+
+def dump_outputs(dirname, name, frame):
+    """Write a frame the timed path returned (rows x W x 4, uint8 or float32) as float32 to
+    dirname/name.npy: whole when it fits DUMP_LIMIT_BYTES, else a sample of its pixels (the same
+    sorted pixel indices for the same shape: a generator seeded with 0), as a (pixels, 4) array."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    a = np.ascontiguousarray(frame, dtype=np.float32)
+    if a.nbytes > DUMP_LIMIT_BYTES:
+        px = a.reshape(-1, a.shape[-1])
+        keep = DUMP_LIMIT_BYTES // (4 * a.shape[-1])
+        a = px[np.sort(np.random.default_rng(0).choice(px.shape[0], keep, replace=False))]
+    np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def lib_sha256():
     """SHA-256 of the loaded product library (profiles are stamped with it)."""
     import hashlib
@@ -320,6 +357,8 @@ def share_ids(ids, count, dev):
 
 def main():
     args = parse()
+    if not args.full and (args.oracle_check or args.verify_frames != 1):
+        raise SystemExit("--oracle-check and --verify-frames belong to the checks of --full")
     # a hung run (e.g. a collective that never completes) shows every thread's stack: on SIGUSR1
     # (the two-rank test sends it before killing the job) and after --watchdog-s
     faulthandler.enable()
@@ -410,8 +449,12 @@ def main():
     # it decides only the sign of a zero direction component (RandomizeDirection, voxel.glsl:132-140).
     # The sun stays where "Make day" puts it: the reference's day/night cycle would move
     # it by ~1e-5 degrees per frame at these frame times.
+    # The count restarts after the device warm-up (a wall-clock budget: its number of frames varies
+    # from run to run), so the W warmup and K timed frames are frames 1 .. W + K of every run.
+    time_base = [0]
+
     def set_frame_time(k):
-        kparams.time = float(k)
+        kparams.time = float(k - time_base[0])
 
     def launch(row0, rows, step, out, prev, cnt_ptr=0, row_block=1):
         sp = torch.cuda.current_stream(dev).cuda_stream   # the part's stream (FrameTiler)
@@ -442,7 +485,7 @@ def main():
 
     def launch_batch(row0, rows, step, outs, pitch, sp, row_block=1):
         # frame batches (FrameTiler batch > 1): the band of len(outs) frames in one launch
-        k0 = tiler.k - len(outs)   # the batch's frames are k0 + 1 .. tiler.k
+        k0 = tiler.k - len(outs) - time_base[0]   # the batch's frames are k0 + 1 .. k0 + len(outs)
         ps = []
         for j in range(len(outs)):
             q = type(kparams).from_buffer_copy(kparams)
@@ -542,6 +585,7 @@ def main():
                             "from ~1.9 to ~2.3 GHz over the first ~150 ms of this load "
                             "(DPM; profiles/r03_s2), so a fresh process's first frames run "
                             "~10 % slower than sustained rendering"}
+    time_base[0] = tiler.k
     watchdog()
     for _ in range(args.warmup):
         tiler.frame()
@@ -606,10 +650,17 @@ def main():
                             for evs in fev_] or None
 
     elapsed, frame_gpu_ms, frame_events_ms = timed_frames(args.steps, args.frame_events)
+    if args.dump_outputs:
+        # what the last timed frame() call returned: this rank's band buffer (one GPU: the frame),
+        # with the per-frame gather rank 0's assembled frame and nothing on the other ranks
+        last = tiler.latest if tiler.gather else tiler.last()
+        if last is not None:
+            dump_outputs(args.dump_outputs, "frame" if rank == 0 else f"frame_rank{rank}",
+                         last.cpu().numpy())
     # The same frames without the per-frame gather (labelled "render_only"): what the split alone
     # sustains, beside the timed gathered frames above
     render_only = None
-    if tiler.gather:
+    if tiler.gather and args.full:
         tiler.exchange_on = False
         ro_el, ro_gpu, _ = timed_frames(args.steps)
         tiler.exchange_on = True
@@ -627,21 +678,24 @@ def main():
     # start / end timestamps (vrt_set_launch_timing: hipExtLaunchKernelGGL events; launches of
     # frames in flight overlap, so a launch lasts longer than frame_gpu_ms / parts). Not in the
     # timed region: the per-launch events cost ~8 % of the frame rate (r02 s17).
-    lt_frames = max(20, min(args.steps, 200))
-    lt_frames -= lt_frames % batch   # whole batches: every launch holds `batch` frames
-    ren.set_launch_timing(lt_frames * parts // batch)
-    for _ in range(lt_frames):
-        tiler.frame()
-    tiler.finish()
-    lt_total, lt_n = ren.launch_timing()
-    ren.set_launch_timing(0)
-    launch_ms = lt_total / max(lt_n, 1)
+    launch_ms = 0.0
+    if args.full:
+        lt_frames = max(20, min(args.steps, 200))
+        lt_frames -= lt_frames % batch   # whole batches: every launch holds `batch` frames
+        ren.set_launch_timing(lt_frames * parts // batch)
+        for _ in range(lt_frames):
+            tiler.frame()
+        tiler.finish()
+        lt_total, lt_n = ren.launch_timing()
+        ren.set_launch_timing(0)
+        launch_ms = lt_total / max(lt_n, 1)
     watchdog()
     # Exchange timing pass (after the timed region; GatherLib only): per frame, device events on its
     # lane stream around the RGB8 pack + ncclGather (from the render's end, so a rank that arrives
     # early also waits there for the slowest rank's band) and around rank 0's assembly
     exchange_t = None
-    if tiler.gather and isinstance(tiler.exchange, GatherLib) and not args.rehearse_gather:
+    if (args.full and tiler.gather and isinstance(tiler.exchange, GatherLib)
+            and not args.rehearse_gather):
         tiler.exchange.timing = []
         for _ in range(max(16, 2 * lanes * batch)):
             tiler.frame()
@@ -671,76 +725,78 @@ def main():
     # what the reference's blocking GL_TIME_ELAPSED query around its one draw measures
     # (main.cpp:350-356); median of 15. And the drop-in's synchronous call (vrt_render_frame:
     # in-lane exact path, two parts) on one GPU: its kernel_ms (device timestamps).
-    lat = []
-    for _ in range(15):
-        torch.cuda.synchronize(dev)
-        if world > 1:
-            dist.barrier()
-        st_ = tiler.next_stream()
-        lane_ = (tiler.k // tiler.batch) % tiler.lanes
-        sts_ = tiler.part_streams[lane_] if tiler.part_streams else [st_]   # every part of the frame
-        ea = [torch.cuda.Event(enable_timing=True) for _ in sts_]
-        eb = [torch.cuda.Event(enable_timing=True) for _ in sts_]
-        for e, s_ in zip(ea, sts_):
-            e.record(s_)
-        tiler.frame()
-        tiler.flush()   # frame batches: the frame alone is a batch of one
-        for e, s_ in zip(eb, sts_):
-            e.record(s_)
-        torch.cuda.synchronize(dev)
-        lat.append(max(a.elapsed_time(b) for a in ea for b in eb))
-    tiler.finish()
-    # Frame batches: a frame is launched only when its batch is full, so the batched pipeline's
-    # latency is one whole batch alone (request of its first frame to completion of the launch)
-    # plus the wait for the batch to fill (batch - 1 frame intervals at the timed frame rate)
-    blat = []
-    if batch > 1:
-        for _ in range(9):
+    latency = None
+    if args.full:
+        lat = []
+        for _ in range(15):
             torch.cuda.synchronize(dev)
             if world > 1:
                 dist.barrier()
+            st_ = tiler.next_stream()
             lane_ = (tiler.k // tiler.batch) % tiler.lanes
-            sts_ = tiler.part_streams[lane_] if tiler.part_streams else [tiler.next_stream()]
+            sts_ = tiler.part_streams[lane_] if tiler.part_streams else [st_]   # every part of the frame
             ea = [torch.cuda.Event(enable_timing=True) for _ in sts_]
             eb = [torch.cuda.Event(enable_timing=True) for _ in sts_]
             for e, s_ in zip(ea, sts_):
                 e.record(s_)
-            for _ in range(batch):
-                tiler.frame()
-            tiler.flush()
+            tiler.frame()
+            tiler.flush()   # frame batches: the frame alone is a batch of one
             for e, s_ in zip(eb, sts_):
                 e.record(s_)
             torch.cuda.synchronize(dev)
-            blat.append(max(a.elapsed_time(b) for a in ea for b in eb))
+            lat.append(max(a.elapsed_time(b) for a in ea for b in eb))
         tiler.finish()
-    lat_t = torch.tensor([float(np.median(lat)), float(np.median(blat)) if blat else 0.0],
-                         dtype=torch.float64, device=dev)
-    if world > 1:
-        dist.all_reduce(lat_t, op=dist.ReduceOp.MAX)
-    latency = {"frame_latency_ms": round(float(np.median(lat)), 4),
-               "frame_latency_ms_max_over_ranks": round(lat_t[0].item(), 4),
-               "what": "one frame alone through the timed path (its lane's launches"
-                       + (", gather and rank 0's assembly" if tiler.gather else "")
-                       + ", device events), median of 15"
-                       + ("; a batch of one: see batch_latency_ms for the batched pipeline" if batch > 1 else ""),
-               "frames_in_flight": lanes * batch,
-               "frames_in_flight_is": "lanes x frames per launch of the timed pipeline (the headline "
-                                      "value's frame rate relies on them; the reference's blocking "
-                                      "GL timer query keeps about one)"}
-    if blat:
-        latency["batch_latency_ms_max_over_ranks"] = round(lat_t[1].item(), 4)
-        latency["batch_latency_is"] = (f"one batch of {batch} frames alone through the timed path "
-                                       "(request of its first frame to the end of its launch and "
-                                       "exchange), median of 9")
-    if world == 1 and not rehearse and rgba8:
-        sync_ms = []
-        for _ in range(9):
-            _, st_d = ren.render_frame(cam, kparams, args.alpha)
-            sync_ms.append(st_d["kernel_ms"])
-        latency["sync_frame_kernel_ms"] = round(float(np.median(sync_ms)), 4)
-        latency["sync_frame_is"] = ("vrt_render_frame (the drop-in's synchronous call: two "
-                                    "interleaved parts, exact path in lane), device timestamps of "
-                                    "its launches, median of 9 (the host copy excluded)")
+        # Frame batches: a frame is launched only when its batch is full, so the batched pipeline's
+        # latency is one whole batch alone (request of its first frame to completion of the launch)
+        # plus the wait for the batch to fill (batch - 1 frame intervals at the timed frame rate)
+        blat = []
+        if batch > 1:
+            for _ in range(9):
+                torch.cuda.synchronize(dev)
+                if world > 1:
+                    dist.barrier()
+                lane_ = (tiler.k // tiler.batch) % tiler.lanes
+                sts_ = tiler.part_streams[lane_] if tiler.part_streams else [tiler.next_stream()]
+                ea = [torch.cuda.Event(enable_timing=True) for _ in sts_]
+                eb = [torch.cuda.Event(enable_timing=True) for _ in sts_]
+                for e, s_ in zip(ea, sts_):
+                    e.record(s_)
+                for _ in range(batch):
+                    tiler.frame()
+                tiler.flush()
+                for e, s_ in zip(eb, sts_):
+                    e.record(s_)
+                torch.cuda.synchronize(dev)
+                blat.append(max(a.elapsed_time(b) for a in ea for b in eb))
+            tiler.finish()
+        lat_t = torch.tensor([float(np.median(lat)), float(np.median(blat)) if blat else 0.0],
+                             dtype=torch.float64, device=dev)
+        if world > 1:
+            dist.all_reduce(lat_t, op=dist.ReduceOp.MAX)
+        latency = {"frame_latency_ms": round(float(np.median(lat)), 4),
+                   "frame_latency_ms_max_over_ranks": round(lat_t[0].item(), 4),
+                   "what": "one frame alone through the timed path (its lane's launches"
+                           + (", gather and rank 0's assembly" if tiler.gather else "")
+                           + ", device events), median of 15"
+                           + ("; a batch of one: see batch_latency_ms for the batched pipeline" if batch > 1 else ""),
+                   "frames_in_flight": lanes * batch,
+                   "frames_in_flight_is": "lanes x frames per launch of the timed pipeline (the headline "
+                                          "value's frame rate relies on them; the reference's blocking "
+                                          "GL timer query keeps about one)"}
+        if blat:
+            latency["batch_latency_ms_max_over_ranks"] = round(lat_t[1].item(), 4)
+            latency["batch_latency_is"] = (f"one batch of {batch} frames alone through the timed path "
+                                           "(request of its first frame to the end of its launch and "
+                                           "exchange), median of 9")
+        if world == 1 and not rehearse and rgba8:
+            sync_ms = []
+            for _ in range(9):
+                _, st_d = ren.render_frame(cam, kparams, args.alpha)
+                sync_ms.append(st_d["kernel_ms"])
+            latency["sync_frame_kernel_ms"] = round(float(np.median(sync_ms)), 4)
+            latency["sync_frame_is"] = ("vrt_render_frame (the drop-in's synchronous call: two "
+                                        "interleaved parts, exact path in lane), device timestamps of "
+                                        "its launches, median of 9 (the host copy excluded)")
 
     # Check of the timed path (after all timing): the next `verify_frames` frames through the same
     # FrameTiler (lanes and parts on their streams, tile order seeded by the frames before
@@ -755,7 +811,7 @@ def main():
     def last_parts():   # this rank's part buffers of the last frame enqueued
         return [tiler.part_rows(tiler.last(), s_) for s_ in range(parts)]
 
-    if not args.no_verify:
+    if args.full and not args.no_verify:
         bad = 0
         total = 0
         vc = torch.zeros_like(cnt)
@@ -816,7 +872,7 @@ def main():
     # Bands that stayed on their ranks (--no-gather): one RCCL gather of the last frame to rank 0
     # (after all timing), the delivery a display of the whole frame would do
     collect = None
-    if world > 1 and not tiler.gather:
+    if args.full and world > 1 and not tiler.gather:
         tiler.finish()
         torch.cuda.synchronize(dev)
         t_c = time.perf_counter()
@@ -830,8 +886,8 @@ def main():
 
     # Per-rank record (multi-rank runs): what a sub-linear scaling curve needs to name its cause
     per_rank = None
-    if world > 1:
-        mine = torch.tensor([frame_gpu_ms, launch_ms, float(np.median(lat)),
+    if args.full and world > 1:
+        mine =torch.tensor([frame_gpu_ms, launch_ms, float(np.median(lat)),
                              exchange_t[0] if exchange_t else -1.0, exchange_t[1] if exchange_t else -1.0],
                             dtype=torch.float64, device=dev)
         allr = [torch.zeros_like(mine) for _ in range(world)]
@@ -878,8 +934,12 @@ def main():
         # frames in flight, launches overlap (launches_in_flight on average), so the GPU's rate is
         # the per-launch rate times that: this rank's bytes per frame / GPU time per frame.
         # (a compositor rank 0 alone, in a rehearsal, has no launch: no per-launch rate)
+        # The per-launch fields come from the launch-timing pass: null without --full.
         per_launch = bytes_per_launch / (launch_ms * 1e-3) / 1e9 if launch_ms > 0 else 0.0
         in_flight = launch_ms * parts / (renderer_gpu_ms * batch)
+
+        def lt(x):
+            return x if args.full else None
         achieved = own_bytes / (renderer_gpu_ms * 1e-3) / 1e9
         lib_hash = lib_sha256()
         traffic = traffic_frame = hbm_frac = None
@@ -910,11 +970,11 @@ def main():
         cpu = None
         oracle_check = None
         frame_o = None
-        cores = host_cores() if world == 1 else None
+        cores = host_cores() if args.full and world == 1 else None
         cam1 = vrt.make_camera(w, h)
         if pairs:   # the oracle renders the first verified frame (its u_Time)
             params.time = pairs[0][2]
-        if world == 1 and args.cpu_seconds > 0:
+        if args.full and world == 1 and args.cpu_seconds > 0:
             threads = args.cpu_threads or cores["threads"]
             cpu, frame_o = cpu_baseline(cam1, vox_host, n, params, args.cpu_seconds, threads)
             cpu.update({k: v for k, v in cores.items() if k != "threads"})
@@ -1000,7 +1060,7 @@ def main():
             },
             "roofline": {
                 "bound": "valu-issue/latency",
-                "achieved": round(per_launch, 2),
+                "achieved": lt(round(per_launch, 2)),
                 "achieved_is": ("reference-normalised algorithmic bytes (1 B per DDA step of the "
                                 "reference walk + 2 B per refraction probe + pixel bytes) of one "
                                 "launch / its mean duration (launch_ms; not a bandwidth: the certified "
@@ -1012,10 +1072,10 @@ def main():
                 "achieved_frame_rate_is": ("the same bytes per frame / GPU time per frame (kernel_ms) "
                                            "= achieved x launches_in_flight: launches of frames in "
                                            "flight overlap"),
-                "launches_in_flight": round(in_flight, 3),
+                "launches_in_flight": lt(round(in_flight, 3)),
                 "peak": HBM_PEAK_GBS,
                 "unit": "GB/s",
-                "frac": round(per_launch / HBM_PEAK_GBS, 4),
+                "frac": lt(round(per_launch / HBM_PEAK_GBS, 4)),
                 "traffic": traffic,
                 "traffic_is": ("measured HBM bytes per launch: rocprofv3 FETCH_SIZE x2 + WRITE_SIZE of a "
                                "one-launch frame (profile stamped with this library's hash) / parts"),
@@ -1024,7 +1084,7 @@ def main():
                 "hbm_frac_is": "measured HBM bytes per frame / GPU time per frame / 8 TB/s",
                 "bytes_per_launch": int(bytes_per_launch),
                 "bytes_per_frame": own_bytes,
-                "launch_ms": round(launch_ms, 4),
+                "launch_ms": lt(round(launch_ms, 4)),
                 "launch_ms_is": ("mean launch duration from the device timestamps of its first "
                                  "kernel's start and last kernel's end (hipExtLaunchKernelGGL "
                                  "events, vrt_set_launch_timing) over a pass of the same frames "

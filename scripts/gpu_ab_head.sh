@@ -12,7 +12,7 @@ for lib in base $(ls build/variants/*.so); do
   if [ $lib = base ]; then unset VRT_LIB; else export VRT_LIB=$PWD/$lib; fi
   for cfgsh in ${CFGS:-"C3:color:1" "C2:color:1" "C4:color:1" "C3:textured:1" "C3:color:8" "C4:color:8"}; do
     IFS=: read cfg sh k <<< "$cfgsh"
-    timeout -k 10 200 python bench.py --config $cfg --shading $sh --rehearse-ranks $k --cpu-seconds 0 --no-verify --steps 400 --warmup 100 $EXTRA > $OUT/${ln}_${cfg}_${sh}_k${k}_$round.log 2>&1 || exit $?
+    timeout -k 10 200 python bench.py --full --config $cfg --shading $sh --rehearse-ranks $k --cpu-seconds 0 --no-verify --steps 400 --warmup 100 $EXTRA > $OUT/${ln}_${cfg}_${sh}_k${k}_$round.log 2>&1 || exit $?
     echo "r$round $ln $cfg $sh k$k $(grep -o '"kernel_ms": [0-9.]*' $OUT/${ln}_${cfg}_${sh}_k${k}_$round.log | head -1)"
   done
 done; done

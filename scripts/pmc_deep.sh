@@ -11,6 +11,6 @@ for cfg in "$@"; do
              "SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_BRANCH SQ_ACTIVE_INST_SCA SQ_INST_CYCLES_SALU"; do
     i=$((i+1))
     timeout -k 10 240 rocprofv3 --pmc $grp -d "$ROOT/$out/${cfg}_g$i" -o run --output-format csv -- \
-      python3 "$ROOT/bench.py" --config "$cfg" --steps 5 --warmup 1 --cpu-seconds 0 --parts 1 > "$ROOT/$out/${cfg}_g$i.log" 2>&1
+      python3 "$ROOT/bench.py" --full --config "$cfg" --steps 5 --warmup 1 --cpu-seconds 0 --parts 1 > "$ROOT/$out/${cfg}_g$i.log" 2>&1
   done
 done

@@ -12,5 +12,5 @@ echo "counters:$have"
 [ -n "$have" ] || exit 1
 set -- $have; [ $# -le 8 ] || exit 1
 timeout -s KILL 120 rocprofv3 --pmc $have -d $OUT/pmc_mix -o run --output-format csv -- \
-  python3 $ROOT/bench.py --config $CFG --steps 5 --warmup 1 --cpu-seconds 0 --parts 1 --no-verify > $OUT/pmc_mix.log 2>&1
+  python3 $ROOT/bench.py --full --config $CFG --steps 5 --warmup 1 --cpu-seconds 0 --parts 1 --no-verify > $OUT/pmc_mix.log 2>&1
 echo "rc=$?"

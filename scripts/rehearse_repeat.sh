@@ -6,7 +6,7 @@ OUT=gpurun_out/$TAG; mkdir -p $OUT
 for i in $(seq 1 $R); do for sh in $SHAPES; do for r in $RANKS; do
   IFS=: read l q <<< "$sh"
   f=$OUT/${CFG}_k${K}_r${r}_l${l}q${q}_$i.log
-  timeout -k 10 120 python bench.py --config $CFG --rehearse-ranks $K --rehearse-rank $r --lanes $l --queues $q \
+  timeout -k 10 120 python bench.py --full --config $CFG --rehearse-ranks $K --rehearse-rank $r --lanes $l --queues $q \
     --steps 400 --warmup 100 --cpu-seconds 0 --no-verify > $f 2>&1 || exit $?
   echo "$CFG k$K r$r lanes $l queues $q run $i $(grep -o '"kernel_ms": [0-9.]*' $f | head -1) $(grep -o '"frame_latency_ms": [0-9.]*' $f | head -1)"
 done; done; done

@@ -67,7 +67,7 @@ def test_bench_four_ranks_rccl_compositor(built):
 def two_ranks(scaling, gather, backend_args, n=2):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}",
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()),
-           os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "6", "--warmup", "2",
+           os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(n), "--steps", "6", "--warmup", "2",
            "--scaling", scaling, "--cpu-seconds", "0", "--watchdog-s", "100"] + backend_args
     cmd += [] if gather else ["--no-gather"]
     env = dict(os.environ, OMP_NUM_THREADS="4")

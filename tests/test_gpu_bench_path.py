@@ -26,7 +26,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.parametrize("alpha", [0.5, 1.0])
 def test_bench_path_c3_three_frames(built, alpha):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "C3", "--steps", "20",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--config", "C3", "--steps", "20",
            "--warmup", "5", "--alpha", str(alpha), "--verify-frames", "3", "--cpu-seconds", "0",
            "--oracle-check", "--frame-events"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=240)
@@ -53,7 +53,7 @@ def test_bench_path_c3_three_frames(built, alpha):
 def test_bench_path_other_configs(built, config):
     """The same end-to-end check for the other BASELINE GPU configs (full size): C1 (glass cube,
     exact primary walks: glass-heavy volume), C2 (terrain 128^3), C4 (terrain 512^3 at 3840x2160)."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", config, "--steps", "10",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--config", config, "--steps", "10",
            "--warmup", "3", "--alpha", "0.5", "--verify-frames", "2", "--cpu-seconds", "0",
            "--oracle-check"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=280)
@@ -65,3 +65,30 @@ def test_bench_path_other_configs(built, config):
     assert v["verified"] and v["mismatched_elements"] == 0 and out["verified"]
     oc = out["oracle_check"]
     assert oc["frames"] == 2 and oc["ok"] and oc["max_lsb"] <= 1
+
+
+def test_plain_run_and_dump(built, tmp_path):
+    """A plain run (no --full) times exactly --steps frames, leaves the fields of the passes it
+    skips null, and with --dump-outputs writes the last timed frame as float32; the same arguments
+    give the same frame in a second process (u_Time restarts after the wall-clock device warm-up)."""
+    import numpy as np
+
+    frames = []
+    for d in ("a", "b"):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", "C0",
+               "--steps", "7", "--warmup", "3", "--dump-outputs", str(tmp_path / d)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=120)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        out = json.loads(lines[0])
+        assert out["steps"] == 7 and out["warmup"] == 3 and out["ms_per_step"] > 0 and out["value"] > 0
+        assert out["unit"] == "Mrays/s" and out["higher_is_better"] is True and out["dtype"] == "f32"
+        for k in ("verify", "verified", "latency", "cpu_baseline", "oracle_check"):
+            assert out[k] is None, k
+        assert out["roofline"]["launch_ms"] is None and out["roofline"]["kernel_ms"] > 0
+        f = np.load(tmp_path / d / "frame.npy")
+        assert f.dtype == np.float32 and f.shape == (400, 400, 4)
+        assert f.min() >= 0 and f.max() <= 255 and np.count_nonzero(f[..., :3]) > 0
+        frames.append(f)
+    assert np.array_equal(frames[0], frames[1])
