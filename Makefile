@@ -10,7 +10,9 @@ HIPFLAGS := -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -ffp-contract=off \
             -fhip-fp32-correctly-rounded-divide-sqrt -fno-slp-vectorize -Iinclude -Wall
 SRC := voxelraytracer_amd/csrc/vrt_render.hip voxelraytracer_amd/csrc/vrt_context.cpp \
        voxelraytracer_amd/csrc/vrt_host.cpp
-HDR := include/vrt.h voxelraytracer_amd/csrc/vrt_internal.h
+CSRC := voxelraytracer_amd/csrc
+HDR := include/vrt.h $(CSRC)/vrt_internal.h $(CSRC)/vrt_tuning.h $(CSRC)/vrt_diag.h $(CSRC)/vrt_math.h \
+       $(CSRC)/vrt_walk.h $(CSRC)/vrt_cert.h $(CSRC)/vrt_aux_kernels.h
 # RCCL: volume broadcast and the frame gather of multi-device contexts (vrt_context.cpp)
 LIBS := -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
 
@@ -33,7 +35,8 @@ build/bin/vrt_headless: examples/headless_app.cpp $(HDR) $(LIBDIR)/libvrt.so
 	    -Wl,-rpath,'$$ORIGIN/../../$(LIBDIR)' -Wl,-rpath,/opt/rocm/lib
 
 # experiment / diagnostic variants for scripts/ab.py, stamps.py, cert_diag.py (never the product
-# library): make variant NAME=w6 DEFS="-DVRT_MIN_WAVES=6", NAME=stamps DEFS=-DVRT_STAMPS
+# library): a numeric knob of vrt_tuning.h (make variant NAME=w6 DEFS="-DVRT_MIN_WAVES=6") or an
+# instrument of vrt_diag.h (NAME=stamps DEFS=-DVRT_STAMPS)
 variant: $(SRC) $(HDR)
 	mkdir -p build/variants
 	$(HIPCC) $(HIPFLAGS) -DVRT_DIAGNOSTIC_BUILD $(DEFS) -shared -o build/variants/libvrt_$(NAME).so $(SRC) $(LIBS)

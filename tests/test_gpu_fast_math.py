@@ -1,4 +1,4 @@
-"""GPU: the kernels' fast correctly rounded reciprocal (vrt_render.hip rcp_newton: the hardware
+"""GPU: the kernels' fast correctly rounded reciprocal (vrt_math.h rcp_newton: the hardware
 reciprocal plus one Newton step on its fma residual, 3 VALU instead of the IEEE division's 11) and
 square root (sqrt_fix: the hardware square root moved by its fma residuals, without the IEEE
 sequence's denormal scaling) equal the IEEE division 1.0f / d and sqrt(s) bit for bit on every

@@ -11,8 +11,8 @@ import pytest
 import voxelraytracer_amd as vrt
 
 pytestmark = pytest.mark.gpu
-CAP = 64  # kDistCap (VRT_DIST_CAP) of csrc/vrt_render.hip
-FWD_CAP = 128  # kFwdCap (VRT_FWD_CAP)
+CAP = 64  # kDistCap of csrc/vrt_walk.h
+FWD_CAP = 128  # kFwdCap (VRT_FWD_CAP, csrc/vrt_tuning.h)
 
 
 def forward_reference(vox, n, octant):

@@ -1,5 +1,5 @@
 """CPU: the closed form of RN(1 / RN(sqrt(s))) for s near 1 that the kernel's normalize3 uses
-(vrt_render.hip near_one_rsqrt) equals IEEE sqrt + division for every float32 within 1024 ulps of 1
+(vrt_math.h near_one_rsqrt) equals IEEE sqrt + division for every float32 within 1024 ulps of 1
 (the kernel's window), restated here bit for bit; and the window is safe by a margin (the closed
 form first fails at 2898 ulps above 1)."""
 import numpy as np

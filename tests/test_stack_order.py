@@ -85,7 +85,7 @@ def test_abi_capacity_never_drops():
 
 
 def cert_tree_order(seed, R, T):
-    """cert_tree (vrt_render.hip): the ray the reference pops next is held in registers, a
+    """cert_tree (vrt_cert.h): the ray the reference pops next is held in registers, a
     reflection ray pushed under a refraction ray waits in ONE per-lane LDS slot; a tree that needs a
     second waiting ray gives up (None: the pixel takes the exact path)."""
     ray = ("p", 0, 0)

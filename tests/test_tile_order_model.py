@@ -9,7 +9,7 @@ import random
 import pytest
 
 CLASSES = 8
-DIV = 4   # VRT_ORD_DIV
+DIV = 4   # kOrdDiv (VRT_ORD_DIV, csrc/vrt_tuning.h)
 
 
 class Band:

@@ -1,0 +1,981 @@
+// vrt_cert.h — the certified walks and nothing else: cert_walk, the certified starts, continuations and
+// bounce trees, texel certification and cert_pixel. Includes vrt_walk.h (and through it vrt_diag.h: CTRACE, CERT_DIAG).
+#ifndef VRT_CERT_H
+#define VRT_CERT_H
+
+#include "vrt_walk.h"
+
+namespace vrt {
+
+// ------------------------------------------------------------ certified walks (stats-free) --
+//
+// The colour-only image depends on a primary walk only through its outcome — miss, or the first
+// event's byte and face axis — and on a shadow walk only through blocked / not blocked
+// (voxel.glsl:395-423: no hit point, length or texel index enters the colour of a non-glass hit;
+// the sky colour depends on the direction alone). The exact walk (skip_walk) replays every DDA
+// step's float state to be bit-identical; the CERTIFIED walk below instead follows the real ray
+// with a float DDA that jumps through the empty boxes of the octant distance field, and returns
+// the exact walk's outcome only when no rounding of the exact walk can change it:
+//  - the exact walk's parameter at any plane crossing differs from the real one by at most
+//    gam_b(u) (`cert_gamma`): its len accumulates at most u*|d|_1 + 3 non-zero steps, each adding
+//    <= 2^-24 len; each t is re-anchored from currentPos (roundings of magnitude <= N + 2, times
+//    1/|d_b|) and then decremented at most K times; zero-length tie steps add no rounding;
+//  - crossings of two axes closer than gam_a + gam_b may come in either order or as a tie: the
+//    cells the exact walk could sample instead (`alternatives`) must be non-events, else UNSURE;
+//  - an event cell is a certified hit only if its entry crossing is isolated (the exact walk
+//    then enters it across the same face, index = that axis) and the length test cannot stop
+//    the walk first; a walk that leaves the volume or whose previous crossing lies beyond the
+//    length budget (by more than the bound) is a certified miss;
+//  - cells with an index N are outside on the path (the exact walk reads the GL_REPEAT plane N
+//    only at a coordinate exactly N, i.e. at a near-edge crossing, where the alternatives read
+//    the padded layout's plane N).
+// UNSURE rays (~0.2 % of pixels at the BASELINE configs, scripts/certsim.py) and every pixel
+// whose primary hit is glass (its secondary rays start at the exact hit point) take the exact
+// path. Only the stats-free colour-only instance uses it: hit records and counters need the
+// exact walk, and textured shading reads the hit point.
+
+enum : int { CERT_MISS = 0, CERT_HIT = 1, CERT_UNSURE = 2 };
+constexpr float kCertMargin = 1.0f / 64.0f;  // jump boxes' forward faces pulled in (position)
+constexpr int kCertMaxIter = 1024;
+constexpr float kCertMaxOrigin = 4e-3f;  // parameter uncertainty of a secondary start beyond which: unsure
+
+struct CertResult {
+  int res;
+  uint32_t byte;
+  int axis;
+  int cx, cy, cz;  // hit cell
+  float u;         // crossing parameter of the hit
+  float eu;        // bound of the exact walk's parameter error there
+  // every step of the exact walk with parameter s < us samples an in-volume cell that is not an
+  // event (the certified crossings before the last one the walk settled); 0: none known
+  float us;
+  CERT_DIAG_ONLY(int iters;)
+};
+
+__device__ __forceinline__ uint32_t cell_texel(const Ctx& c, int i, int j, int k, uint32_t obase) {
+  return load_u16_at(c.vox, mad24(mad24(uint32_t(k), c.p, uint32_t(j)), c.p, uint32_t(i)), obase);
+}
+// texel of a cell on the certified path: cells outside [0, N)^3 read 0 (empty, G = 0)
+__device__ __forceinline__ uint32_t path_texel(const Ctx& c, int i, int j, int k, uint32_t obase) {
+  const uint32_t n = uint32_t(c.n);
+  if (uint32_t(i) >= n || uint32_t(j) >= n || uint32_t(k) >= n) return 0u;
+  return cell_texel(c, i, j, k, obase);
+}
+// byte of a cell the exact walk might sample at a near-edge crossing (plane N: GL_REPEAT copy)
+__device__ __forceinline__ uint32_t alt_byte(const Ctx& c, int i, int j, int k, uint32_t obase) {
+  const uint32_t n = uint32_t(c.n);
+  if (uint32_t(i) > n || uint32_t(j) > n || uint32_t(k) > n) return 0u;
+  return cell_texel(c, i, j, k, obase) & kVoxMask;
+}
+// an event of the exact walk: shadow rays stop at opaque bytes (not air, not glass), other rays
+// at any byte other than their medium's (voxel.glsl:353, :357)
+template <bool SHADOW>
+__device__ __forceinline__ bool cert_event(uint32_t b, uint32_t medium) {
+  return SHADOW ? (b & ~2u) != 0u : b != medium;
+}
+
+// Certified walk from P along D (every |d| in the fast-path range) with rcp ~ 1/D (a few ulp
+// suffice: the walk's own rounding is inside the 4e-5 allowance of the bound), starting in cell
+// (cx, cy, cz) inside the volume. U = max_len - len0: the exact walk samples the crossing at u iff
+// its len before that step is < max_len. e0: parameter uncertainty of the start (a shadow origin
+// is the exact primary hit point, known to +-e0 along the primary); ed: per-axis crossing-order
+// uncertainty from it; len0b: bound of len0. No crossing lies behind the start, so the start
+// cell's box need not cover a cell behind it: it is read from the diagonal neighbour's texel,
+// G(v + s) = F(v) - 1, i.e. the box [v, v + G s].
+template <bool SHADOW>
+__device__ __forceinline__ CertResult cert_walk(const Ctx& c, const f3 P, const f3 D, const f3 rcp, const float U,
+                                int cx, int cy, int cz, const float e0, const f3 ed,
+                                const float len0b, const uint32_t medium, const uint32_t tex0 = ~0u) {
+  CertResult r;
+  r.res = CERT_UNSURE;
+  r.byte = 0u;
+  r.axis = 0;
+  r.cx = r.cy = r.cz = 0;
+  r.u = 0.0f;
+  r.eu = 0.0f;
+  r.us = 0.0f;
+  const int sx = D.x > 0.0f ? 1 : -1, sy = D.y > 0.0f ? 1 : -1, sz = D.z > 0.0f ? 1 : -1;
+  const int ux = D.x > 0.0f ? 1 : 0, uy = D.y > 0.0f ? 1 : 0, uz = D.z > 0.0f ? 1 : 0;
+  const f3 ar = mk(__builtin_fabsf(rcp.x), __builtin_fabsf(rcp.y), __builtin_fabsf(rcp.z));
+  const float l1 = __builtin_fabsf(D.x) + __builtin_fabsf(D.y) + __builtin_fabsf(D.z);
+  const uint32_t obase = ((D.x < 0.0f ? 1u : 0u) | (D.y < 0.0f ? 2u : 0u) | (D.z < 0.0f ? 4u : 0u)) * c.ostride;
+  // Rounding bounds as polynomials in the crossing parameter u (2x safety factor on 2^-24):
+  //   K(u) = u |d|_1 + 3 non-zero exact steps, sum_k len_k <= (K + 3)^2 / (2 |d|_1) + K (len0 + 1),
+  //   gam_b(u) = 2^-24 (sum len + 2 (u + len0) + (K + 3N + 8) |1/d_b|) + 4e-5 + e0 + ed_b,
+  //   gL(u) = 2^-23 sum len + 1e-4 + e0 (the length test)
+  constexpr float k24 = 2.0f * 0x1p-24f;
+  const float q2 = 0.5f * k24 * l1;
+  // 18 / |d|_1 only bounds a sum: the hardware reciprocal (<= 1 ulp) scaled up by 2^-19 stays above it
+  const float lin = 6.0f + l1 * (len0b + 1.0f),
+              con = (18.0f * 1.0000020f) * __builtin_amdgcn_rcpf(l1) + 3.0f * (len0b + 1.0f);
+  const float nterm = 3.0f * c.fn + 11.0f;
+  const f3 q1 = mk(k24 * (lin + 2.0f + ar.x * l1), k24 * (lin + 2.0f + ar.y * l1), k24 * (lin + 2.0f + ar.z * l1));
+  const float c0 = k24 * (con + 2.0f * len0b) + 4e-5f + e0;
+  const f3 q0 = mk(c0 + k24 * ar.x * nterm + ed.x, c0 + k24 * ar.y * nterm + ed.y, c0 + k24 * ar.z * nterm + ed.z);
+  const float g2 = 2.0f * q2, g1 = 2.0f * k24 * lin, g0 = 2.0f * k24 * con + 1e-4f + e0;
+  // sign-folded start and direction: Ps_b + u |d_b| = s_b (P_b + u d_b) exactly (negation is exact),
+  // so a landing cell is floor(s x) ^ m, m = 0 or ~0 (ceil(x) - 1 = ~floor(-x)), without branches
+  const f3 Ps = mk(ux ? P.x : -P.x, uy ? P.y : -P.y, uz ? P.z : -P.z);
+  const f3 Da = mk(__builtin_fabsf(D.x), __builtin_fabsf(D.y), __builtin_fabsf(D.z));
+  const int mx = ux - 1, my = uy - 1, mz = uz - 1;
+  f3 sig = mk((float(cx + ux) - P.x) * rcp.x, (float(cy + uy) - P.y) * rcp.y,
+              (float(cz + uz) - P.z) * rcp.z);
+  // start: the unguarded box from the diagonal neighbour (G(v + s) + 1 in the guarded formula)
+  // (tex0: that texel, loaded by the caller beside an earlier load; ~0u: load it here)
+  uint32_t tex = (tex0 != ~0u ? tex0 : path_texel(c, cx + sx, cy + sy, cz + sz, obase)) + (1u << kDistShift);
+  CTRACE(c, 100 + int(SHADOW), cx, cy, cz, P.x, P.y, P.z, U);
+  CTRACE(c, 101, D.x, D.y, D.z, e0, ed.x, ed.y, ed.z);
+  CERT_DIAG_ONLY(r.iters = 0;)
+  for (int guard = 0; guard < kCertMaxIter; ++guard) {
+    CERT_DIAG_ONLY(r.iters = guard + 1;)
+    const float s1 = __builtin_fminf(sig.x, __builtin_fminf(sig.y, sig.z));
+    const int a = sig.x == s1 ? 0 : (sig.y == s1 ? 1 : 2);
+    const float uu = gmax(s1, 0.0f);
+    const f3 gam = mk(__builtin_fmaf(__builtin_fmaf(q2, uu, q1.x), uu, q0.x),
+                      __builtin_fmaf(__builtin_fmaf(q2, uu, q1.y), uu, q0.y),
+                      __builtin_fmaf(__builtin_fmaf(q2, uu, q1.z), uu, q0.z));
+    // empty-space jump: the box [v - s, v + (G - 1) s] of this cell is empty and in the volume
+    // (only for rays in air: empty cells are events in a glass medium)
+    const uint32_t G = tex >> kDistShift;
+    if (G >= 2u && (SHADOW || medium == 0u)) {
+      // the box's far face on axis b is G - 1 - margin cells beyond the plane of sig_b: its
+      // parameter sig_b + (G - 1 - margin) |1/d_b| up to a few ulps, far inside the margin's
+      // margin |1/d_b| (|sig_b| <= ~400 |1/d_b| in a 256^3 volume: 1e-4 |1/d_b| at 3 ulps)
+      const float fg1 = float(G) - (1.0f + kCertMargin);
+      const float lx = __builtin_fmaf(fg1, ar.x, sig.x);
+      const float ly = __builtin_fmaf(fg1, ar.y, sig.y);
+      const float lz = __builtin_fmaf(fg1, ar.z, sig.z);
+      // per axis: the exact walk crosses the box face of axis b within gam_b of l_b, so its steps
+      // up to min_b (l_b - gam_b) sample box cells (a common max(gam) would let one nearly
+      // parallel axis, |1/d_b| huge, stop every jump: ~90 us cell-by-cell walks at C3)
+      const float uj = __builtin_fminf(__builtin_fminf(lx - gam.x, ly - gam.y),
+                                       __builtin_fminf(lz - gam.z, U + 2.0f));
+      CTRACE(c, 102, G, s1, uj, gam.x, gam.y, gam.z, 0);
+      if (uj > s1) {
+        // the cell the exact walk is in there: floor(x) moving up, ceil(x) - 1 moving down
+        const float x = Ps.x + uj * Da.x, y = Ps.y + uj * Da.y, z = Ps.z + uj * Da.z;
+        cx = int(__builtin_floorf(x)) ^ mx;
+        cy = int(__builtin_floorf(y)) ^ my;
+        cz = int(__builtin_floorf(z)) ^ mz;
+        sig = mk((float(cx + ux) - P.x) * rcp.x, (float(cy + uy) - P.y) * rcp.y,
+                 (float(cz + uz) - P.z) * rcp.z);
+        tex = path_texel(c, cx, cy, cz, obase);
+        continue;
+      }
+    }
+    // one crossing, s1 on axis a; prev = the crossing before it (the exact walk's len there)
+    const f3 back = mk(sig.x - ar.x, sig.y - ar.y, sig.z - ar.z);
+    const float mback = gmax(back.x, gmax(back.y, back.z));
+    const float prev = gmax(mback, 0.0f);
+    const float gL = __builtin_fmaf(__builtin_fmaf(g2, uu, g1), uu, g0);
+    if (prev > U + gL) {
+      // the length test stops the walk before this crossing, unless a tie merges it into the
+      // step of the one before (that step passed the test): then the exact walk still samples it
+      // (a tree ray whose y and z crossings tied at len 101.1 left the glass there, refracting,
+      // before its length ended the march; its sky colour took the refracted direction)
+      if (s1 - mback < 2.0f * gmax(gam.x, gmax(gam.y, gam.z))) return r;
+      r.res = CERT_MISS;
+      return r;
+    }
+    const int nx = cx + (a == 0 ? sx : 0), ny = cy + (a == 1 ? sy : 0), nz = cz + (a == 2 ? sz : 0);
+    const uint32_t ntex = path_texel(c, nx, ny, nz, obase);
+    const float ga = a == 0 ? gam.x : (a == 1 ? gam.y : gam.z);
+    // near-edge flags per other axis: ahead (crossed within the bound after s1) / behind (before).
+    // A plane behind counts down to -gam_b, not 0: a ray that starts ON a plane (a shadow or
+    // secondary ray from an exact hit point on the hit face) has that plane at parameter 0 up to
+    // rounding, and the exact walk's currentPos stays on it — sampling the voxel beyond it — until
+    // the ray has moved half an ulp of the coordinate off it (r02 s18: a shadow ray from
+    // (33.000008, 127, 37.02) sampled the panel voxel (32, 127, 37) at its first x crossing, and
+    // back.y rounded to just below 0 hid that alternative from the certified walk)
+    // nf bits 0-2: ahead x, y, z; 3-5: behind x, y, z. They are rare: a superset test first (the
+    // second smallest sig bounds every sig_b, b != a, from below, the latest back every back_b from
+    // above, and ga + max gam every ga + gam_b; rounding is monotone), the flags only if it holds.
+    const float tg = ga + gmax(gam.x, gmax(gam.y, gam.z));
+    // the crossings up to prev are settled (this one, at s1, may not be): an exact step at s <
+    // prev - tg has its real crossing before prev (gam_b <= tg), so it samples a settled cell
+    r.us = prev - tg - 1e-3f;
+    uint32_t nf = 0u;
+    if (__builtin_amdgcn_fmed3f(sig.x, sig.y, sig.z) - s1 < tg || s1 - mback < tg) {
+      const bool ahx = a != 0 && sig.x - s1 < ga + gam.x, ahy = a != 1 && sig.y - s1 < ga + gam.y,
+                 ahz = a != 2 && sig.z - s1 < ga + gam.z;
+      const bool bhx = a != 0 && back.x > -gam.x && s1 - back.x < ga + gam.x;
+      const bool bhy = a != 1 && back.y > -gam.y && s1 - back.y < ga + gam.y;
+      const bool bhz = a != 2 && back.z > -gam.z && s1 - back.z < ga + gam.z;
+      nf = uint32_t(ahx) | uint32_t(ahy) << 1 | uint32_t(ahz) << 2 | uint32_t(bhx) << 3 |
+           uint32_t(bhy) << 4 | uint32_t(bhz) << 5;
+    }
+    const uint32_t nb = ntex & kVoxMask;
+    CTRACE(c, 103, nx, ny, nz, s1, a, nf, nb);
+    CTRACE(c, 104, cx, cy, cz, sig.x, sig.y, sig.z, ga);
+    if (cert_event<SHADOW>(nb, medium)) {
+      if (!(prev + gL < U)) return r;  // the length test might stop the walk first
+      if (nf == 0u) {
+        r.res = CERT_HIT;
+        r.byte = nb;
+        r.axis = a;
+        r.cx = nx;
+        r.cy = ny;
+        r.cz = nz;
+        r.u = s1;
+        r.eu = ga;
+        return r;
+      }
+      if (SHADOW && __builtin_popcount(nf) == 1) {
+        // blocked whichever way the exact walk goes: near-behind b still samples nc (or nc - e_b
+        // first); near-ahead b samples nc, or cell + e_b and then nc + e_b
+        bool ok = true;
+        if (nf & 7u) {
+          const int bx = (nf & 1u) ? sx : 0, by = (nf & 2u) ? sy : 0, bz = (nf & 4u) ? sz : 0;
+          ok = cert_event<true>(alt_byte(c, cx + bx, cy + by, cz + bz, obase), 0u) ||
+               cert_event<true>(alt_byte(c, nx + bx, ny + by, nz + bz, obase), 0u);
+        }
+        if (ok) {
+          r.res = CERT_HIT;
+          r.byte = nb;
+        }
+      }
+      return r;  // hit or unsure
+    }
+    if (nf) {  // cells the exact walk may sample instead of the path's: all must be non-events
+      const bool ahx = nf & 1u, ahy = nf & 2u, ahz = nf & 4u, bhx = nf & 8u, bhy = nf & 16u,
+                 bhz = nf & 32u;
+      const int nah = int(ahx) + int(ahy) + int(ahz);
+      if (__builtin_popcount(nf) >= 2) {  // near a corner: the 2x2x2 block ahead and the cells behind nc
+        for (int q = 1; q < 8; ++q)
+          if (cert_event<SHADOW>(alt_byte(c, cx + ((q & 1) ? sx : 0), cy + ((q & 2) ? sy : 0),
+                                          cz + ((q & 4) ? sz : 0), obase), medium))
+            return r;
+        if ((bhx && cert_event<SHADOW>(alt_byte(c, nx - sx, ny, nz, obase), medium)) ||
+            (bhy && cert_event<SHADOW>(alt_byte(c, nx, ny - sy, nz, obase), medium)) ||
+            (bhz && cert_event<SHADOW>(alt_byte(c, nx, ny, nz - sz, obase), medium)))
+          return r;
+      } else if (nah) {  // b may be crossed first, or tie: cell + e_b, nc + e_b
+        const int bx = ahx ? sx : 0, by = ahy ? sy : 0, bz = ahz ? sz : 0;
+        if (cert_event<SHADOW>(alt_byte(c, cx + bx, cy + by, cz + bz, obase), medium) ||
+            cert_event<SHADOW>(alt_byte(c, nx + bx, ny + by, nz + bz, obase), medium))
+          return r;
+      } else {  // a may have been crossed before b: nc - e_b
+        if (cert_event<SHADOW>(alt_byte(c, nx - (bhx ? sx : 0), ny - (bhy ? sy : 0),
+                                        nz - (bhz ? sz : 0), obase), medium))
+          return r;
+      }
+    }
+    const int na = a == 0 ? nx : (a == 1 ? ny : nz);
+    const int sa = a == 0 ? sx : (a == 1 ? sy : sz);
+    if (uint32_t(na) >= uint32_t(c.n)) {  // left the volume (moving away on axis a)
+      r.res = CERT_MISS;
+      return r;
+    }
+    cx = nx;
+    cy = ny;
+    cz = nz;
+    tex = ntex;
+    const float np = float(na + (sa > 0 ? 1 : 0));
+    if (a == 0) sig.x = (np - P.x) * rcp.x;
+    else if (a == 1) sig.y = (np - P.y) * rcp.y;
+    else sig.z = (np - P.z) * rcp.z;
+  }
+  return r;
+}
+
+// A ray that starts at a face crossing of a certified walk (a shadow or secondary ray from a hit,
+// or a walk restarted by in-volume refraction): the exact origin lies within e (parameter) of
+// X = P + u D0 along the parent direction D0, so within e |D0_fa| of the face plane (axis fa),
+// possibly on its far side. The exact walk starts in the same cell (cx, cy, cz) on the new
+// direction's side of the plane and samples the same cells if, on every other axis, X is farther
+// than its uncertainty from a plane and the new ray's first crossing of that axis comes after it
+// has left the face plane's neighbourhood (lead). ed: the crossing-order uncertainty the origin
+// adds to the new walk.
+__device__ __forceinline__ bool cert_start(const f3 X, const f3 D0, const f3 Dn, const f3 rcpn,
+                                           int fa, float e, int cx, int cy, int cz, f3& ed) {
+  ed = mk(2.0f * e * __builtin_fabsf(D0.x * rcpn.x), 2.0f * e * __builtin_fabsf(D0.y * rcpn.y),
+          2.0f * e * __builtin_fabsf(D0.z * rcpn.z));
+  const float d0a = fa == 0 ? D0.x : (fa == 1 ? D0.y : D0.z);
+  const float rna = fa == 0 ? rcpn.x : (fa == 1 ? rcpn.y : rcpn.z);
+  const float lead = (e * __builtin_fabsf(d0a) + 1e-5f) * __builtin_fabsf(rna);
+  const float wx = (float(cx + (Dn.x > 0.0f)) - X.x) * rcpn.x;
+  const float wy = (float(cy + (Dn.y > 0.0f)) - X.y) * rcpn.y;
+  const float wz = (float(cz + (Dn.z > 0.0f)) - X.z) * rcpn.z;
+  const f3 fr = mk(X.x - __builtin_floorf(X.x), X.y - __builtin_floorf(X.y), X.z - __builtin_floorf(X.z));
+  const f3 dm = mk(e * __builtin_fabsf(D0.x) + 2e-5f, e * __builtin_fabsf(D0.y) + 2e-5f,
+                   e * __builtin_fabsf(D0.z) + 2e-5f);
+  const bool okx = fa == 0 || (wx >= lead + ed.x + 1e-4f && fr.x >= dm.x && 1.0f - fr.x >= dm.x);
+  const bool oky = fa == 1 || (wy >= lead + ed.y + 1e-4f && fr.y >= dm.y && 1.0f - fr.y >= dm.y);
+  const bool okz = fa == 2 || (wz >= lead + ed.z + 1e-4f && fr.z >= dm.z && 1.0f - fr.z >= dm.z);
+  return okx && oky && okz;
+}
+
+// The cell before a hit cell along D on its crossed axis
+__device__ __forceinline__ void cell_before(const CertResult& h, const f3 D, int& x, int& y, int& z) {
+  x = h.cx - (h.axis == 0 ? (D.x > 0.0f ? 1 : -1) : 0);
+  y = h.cy - (h.axis == 1 ? (D.y > 0.0f ? 1 : -1) : 0);
+  z = h.cz - (h.axis == 2 ? (D.z > 0.0f ? 1 : -1) : 0);
+}
+
+// A Hit record for a certified hit of `ray`: point and len approximate (within h.eu along the
+// ray); only the face, voxel and (in robust positions) the probes derived from it are used
+__device__ __forceinline__ Hit cert_hit_record(const Ray& ray, const CertResult& h) {
+  Hit hh;
+  hh.found = true;
+  hh.voxel = h.byte;
+  hh.axis = h.axis;
+  hh.vidx = -1;
+  hh.len = ray.len + h.u;
+  hh.point = mk(ray.pos.x + h.u * ray.dir.x, ray.pos.y + h.u * ray.dir.y, ray.pos.z + h.u * ray.dir.z);
+  hh.normal = mk(0.0f, 0.0f, 0.0f);
+  set_comp(hh.normal, h.axis, -gsign(comp(ray.dir, h.axis)));
+  return hh;
+}
+
+// TraceWithShadow's colour update (voxel.glsl:395-418) for a certified hit of `ray`: the shadow
+// bit by a certified shadow walk from the hit, unless it cannot change the brightness (lit ==
+// ambient). false: unsure (colour untouched).
+template <bool TEX = false>
+__device__ __forceinline__ bool cert_shade_hit(const Ctx& c, const Ray& ray, const CertResult& h,
+                                               const Hit& hh, f3& color, float4 col = float4()) {
+  const float lit = lit_brightness<TEX>(hh, c.sun_n, ray.dir);
+  float brightness = kAmbient;
+  if (lit != kAmbient && !shadow_free_hit(h.byte, TEX)) {  // otherwise the brightness is the ambient term (or irrelevant)
+    const f3 S = c.sun_n;
+    if (!(dot3(hh.normal, S) > 0.0f) || !fast_path_ok(S)) { CERT_DIAG(5); return false; }  // back face
+    // shadow origin: the exact hit point; start cell: the air cell in front of the hit face
+    int ax, ay, az;
+    cell_before(h, ray.dir, ax, ay, az);
+    // the shadow walk's start texel (the diagonal neighbour in the sun's octant volume) is loaded
+    // first, so its latency overlaps the start checks and the air-cell load (same octant volume:
+    // every octant volume holds the same voxel bytes)
+    const uint32_t sob = ((S.x < 0.0f ? 1u : 0u) | (S.y < 0.0f ? 2u : 0u) | (S.z < 0.0f ? 4u : 0u)) * c.ostride;
+    const uint32_t t0 = path_texel(c, ax + (S.x > 0.0f ? 1 : -1), ay + (S.y > 0.0f ? 1 : -1),
+                                   az + (S.z > 0.0f ? 1 : -1), sob);
+    f3 ed;
+    if (!cert_start(hh.point, ray.dir, S, c.sun_rcp, h.axis, h.eu, ax, ay, az, ed)) {
+      CERT_DIAG(6);
+      return false;
+    }
+    const uint32_t n = uint32_t(c.n);
+    if (uint32_t(ax) >= n || uint32_t(ay) >= n || uint32_t(az) >= n) { CERT_DIAG(7); return false; }
+    if (cert_event<true>(cell_texel(c, ax, ay, az, sob) & kVoxMask, 0u)) { CERT_DIAG(7); return false; }
+    const CertResult s = cert_walk<true>(c, hh.point, S, c.sun_rcp, c.max_len - hh.len, ax, ay, az,
+                                         h.eu, ed, hh.len, 0u, t0);
+    if (s.res == CERT_UNSURE) { CERT_DIAG(8); return false; }
+    CERT_DIAG(9);
+    brightness = s.res == CERT_HIT ? kAmbient : lit;
+  } else {
+    CERT_DIAG(4);
+  }
+  if (!TEX) col = get_color<false>(c, hh);  // textured: the certified texel (cert_texel)
+  color.x = mixf(color.x, col.x * col.w * brightness, ray.energy);
+  color.y = mixf(color.y, col.y * col.w * brightness, ray.energy);
+  color.z = mixf(color.z, col.z * col.w * brightness, ray.energy);
+  return true;
+}
+
+// RayMarch (voxel.glsl:302-384) of a secondary ray by certified walks; `ray` is inout as in
+// march(): leaving a glass medium refracts it in place (:357-380), and the walk restarts from
+// that crossing. (cx, cy, cz), e0, ed: the start (cert_start). Returns the first non-air event
+// (CERT_HIT), CERT_MISS or CERT_UNSURE.
+__device__ __forceinline__ CertResult cert_march(const Ctx& c, Ray& ray, int cx, int cy, int cz, float e0, f3 ed) {
+  CertResult h;
+  h.res = CERT_UNSURE;
+  uint32_t medium = ray.voxel;
+  int internal = 0;
+  for (int seg = 0; seg < 32; ++seg) {
+    if (!fast_path_ok(ray.dir) || !(e0 < kCertMaxOrigin)) { CERT_DIAG(24); return h; }
+    const f3 rcp = mk(__builtin_amdgcn_rcpf(ray.dir.x), __builtin_amdgcn_rcpf(ray.dir.y),
+                      __builtin_amdgcn_rcpf(ray.dir.z));
+    h = cert_walk<false>(c, ray.pos, ray.dir, rcp, c.max_len - ray.len, cx, cy, cz, e0, ed, ray.len,
+                         medium);
+    if (h.res == CERT_UNSURE) CERT_DIAG(25);
+    if (h.res != CERT_HIT || h.byte != 0u) return h;
+    CERT_DIAG(30);
+    // in-volume refraction at the crossing into the air cell (h.cx, h.cy, h.cz)
+    h.res = CERT_UNSURE;
+    const Hit eh = cert_hit_record(ray, h);
+    const f3 D0 = ray.dir;
+    // the probes at point +- normal/2 (:219-220) read the exact point's cells if the point is
+    // robust on the other axes
+    const f3 fr = mk(eh.point.x - __builtin_floorf(eh.point.x), eh.point.y - __builtin_floorf(eh.point.y),
+                     eh.point.z - __builtin_floorf(eh.point.z));
+    const f3 dm = mk(h.eu * __builtin_fabsf(D0.x) + 2e-5f, h.eu * __builtin_fabsf(D0.y) + 2e-5f,
+                     h.eu * __builtin_fabsf(D0.z) + 2e-5f);
+    if ((h.axis != 0 && !(fr.x >= dm.x && 1.0f - fr.x >= dm.x)) ||
+        (h.axis != 1 && !(fr.y >= dm.y && 1.0f - fr.y >= dm.y)) ||
+        (h.axis != 2 && !(fr.z >= dm.z && 1.0f - fr.z >= dm.z))) {
+      CERT_DIAG(26);
+      return h;
+    }
+    // position-independent directions only (RandomizeDirection's zero-noise identity)
+    const float eta = mat_refr(get_voxel(c, eh.point + eh.normal * 0.5f)) /
+                      mat_refr(get_voxel(c, eh.point - eh.normal * 0.5f));
+    const f3 rd = refract3(normalize3(D0), eh.normal, eta);
+    const bool tir = rd.x == 0.0f && rd.y == 0.0f && rd.z == 0.0f;
+    if (tir ? !(c.refl_noise == 0.0f && zero_noise_exact(reflect3(D0, eh.normal)))
+            : !(c.refr_noise == 0.0f && zero_noise_exact(rd))) {
+      CERT_DIAG(27);
+      return h;
+    }
+    Counters kk;
+#pragma unroll
+    for (int q = 0; q < VRT_CNT_COUNT; ++q) kk.c[q] = 0;
+    Ray nr = refraction_ray<false>(c, ray, eh, kk);
+    nr.tdepth--;
+    if (nr.voxel == medium) {
+      internal++;
+      if (internal > 10) {
+        nr.dir = D0;
+        nr.voxel = 0u;
+      }
+    }
+    medium = nr.voxel;
+    // restart cell: the crossed cell, or the one before it when the direction turned back
+    int nx = h.cx, ny = h.cy, nz = h.cz;
+    if ((comp(nr.dir, h.axis) > 0.0f) != (comp(D0, h.axis) > 0.0f)) cell_before(h, D0, nx, ny, nz);
+    if (!fast_path_ok(nr.dir)) { CERT_DIAG(28); return h; }
+    const f3 rcpn = mk(__builtin_amdgcn_rcpf(nr.dir.x), __builtin_amdgcn_rcpf(nr.dir.y),
+                       __builtin_amdgcn_rcpf(nr.dir.z));
+    f3 edn;
+    if (!cert_start(eh.point, D0, nr.dir, rcpn, h.axis, h.eu, nx, ny, nz, edn)) { CERT_DIAG(28); return h; }
+    ray = nr;
+    const uint32_t n = uint32_t(c.n);
+    if (uint32_t(nx) >= n || uint32_t(ny) >= n || uint32_t(nz) >= n) {
+      // out of the volume across the crossed face, moving away: TestCube ends the walk
+      h.res = CERT_MISS;
+      return h;
+    }
+    cx = nx;
+    cy = ny;
+    cz = nz;
+    e0 = h.eu;
+    ed = edn;
+  }
+  CERT_DIAG(29);
+  h.res = CERT_UNSURE;
+  return h;
+}
+
+// ------------------------------------------------------------ certified bounce trees --------
+//
+// The colour of a glass pixel's bounce tree (voxel.glsl:425-452) depends on the exact hit points
+// only through the walks' outcomes: reflection and refraction directions, Fresnel energies, the
+// sky colour and the brightness are functions of directions and face normals alone
+// (:162-165, :203-246, :386-423) once RandomizeDirection is the identity (noise 0, no -0
+// component), and the accumulated rayLength enters only through the `< u_MaxRayLength` test. So
+// every ray of the tree is walked by a certified walk from its uncertain origin: the parent's
+// certified hit, known to its bound eu along the parent (cert_start checks the start cell and
+// turns the origin uncertainty into per-axis crossing-order bounds; cert_march carries in-volume
+// refraction). Any unsure step sends the whole pixel to the exact path.
+//
+// A ray in flight is a TreeRay: the Ray the reference would carry (pos and len approximate, dir,
+// energy, medium and depths exact) plus its certified start. The DFS keeps the ray the reference
+// pops next in registers (the last-pushed child), so only a reflection ray pushed under a
+// refraction ray waits, in one per-lane LDS slot; a tree that would hold two such rays at once (never at the BASELINE configs: one glass voxel or
+// one-voxel glass walls) goes to the exact path.
+struct TreeRay {
+  Ray ray;
+  int cx, cy, cz;  // start cell (the exact walk's first cell)
+  float e0;        // origin uncertainty (parameter along the parent)
+  f3 ed;           // per-axis crossing-order uncertainty from it
+};
+// The slot: 12 words in the lane's own 3 float4s (lane-major; in the in-lane instances the exact
+// walk's axis table, c.ax) and 2 words component-major at b[0], b[NL] (there the bounce stack's
+// bottom entry): both regions belong to this lane alone, and it is done with the tree before its
+// exact path (if any) uses them. (A slot striped over the whole workgroup's pool would overwrite
+// the other wave's axis table in the middle of its exact walks.)
+constexpr int kTreeWords = 14;
+template <int NL>
+__device__ __forceinline__ void tree_put(float4* __restrict__ a, float* __restrict__ b, const TreeRay& t) {
+  a[0] = make_float4(t.ray.pos.x, t.ray.pos.y, t.ray.pos.z, t.ray.dir.x);
+  a[1] = make_float4(t.ray.dir.y, t.ray.dir.z, t.ray.len, t.ray.energy);
+  a[2] = make_float4(t.e0, t.ed.x, t.ed.y, t.ed.z);
+  // cells in [0, 1024); a stored ray is a reflection ray: medium air
+  b[0] = __uint_as_float(uint32_t(t.cx) | uint32_t(t.cy) << 10 | uint32_t(t.cz) << 20);
+  b[NL] = __uint_as_float(uint32_t(t.ray.rdepth) | uint32_t(t.ray.tdepth) << 16);
+}
+template <int NL>
+__device__ __forceinline__ TreeRay tree_get(const float4* __restrict__ a, const float* __restrict__ b) {
+  TreeRay t;
+  const float4 a0 = a[0], a1 = a[1], a2 = a[2];
+  t.ray.pos = mk(a0.x, a0.y, a0.z);
+  t.ray.dir = mk(a0.w, a1.x, a1.y);
+  t.ray.len = a1.z;
+  t.ray.energy = a1.w;
+  t.e0 = a2.x;
+  t.ed = mk(a2.y, a2.z, a2.w);
+  const uint32_t w = __float_as_uint(b[0]);
+  t.cx = int(w & 1023u);
+  t.cy = int((w >> 10) & 1023u);
+  t.cz = int((w >> 20) & 1023u);
+  const uint32_t dp = __float_as_uint(b[NL]);
+  t.ray.rdepth = int(dp & 0xffffu);
+  t.ray.tdepth = int(dp >> 16);
+  t.ray.voxel = 0u;
+  return t;
+}
+
+// The certified start of a child ray from the certified hit h of its parent (direction d0 there):
+// the start cell, checked inside the volume, and cert_start's bounds. false: unsure.
+__device__ __forceinline__ bool tree_start(const Ctx& c, const CertResult& h, const Hit& hh, const f3 d0,
+                                           TreeRay& t) {
+  if (!fast_path_ok(t.ray.dir)) return false;
+  const uint32_t n = uint32_t(c.n);
+  if (uint32_t(t.cx) >= n || uint32_t(t.cy) >= n || uint32_t(t.cz) >= n) { CERT_DIAG(31); return false; }
+  const f3 rn = mk(__builtin_amdgcn_rcpf(t.ray.dir.x), __builtin_amdgcn_rcpf(t.ray.dir.y),
+                   __builtin_amdgcn_rcpf(t.ray.dir.z));
+  t.e0 = h.eu;
+  return cert_start(hh.point, d0, t.ray.dir, rn, h.axis, h.eu, t.cx, t.cy, t.cz, t.ed);
+}
+
+// GetReflectionRay (voxel.glsl:203-215) of a certified hit: the direction must not depend on the
+// point (RandomizeDirection's zero-noise identity); it starts back in the cell before the face
+template <bool TEX>
+__device__ __forceinline__ bool tree_reflection(const Ctx& c, const Ray& ray, const CertResult& h, const Hit& hh,
+                                                TreeRay& t) {
+  if (!(c.refl_noise == 0.0f && zero_noise_exact(reflect3(ray.dir, hh.normal)))) return false;
+  t.ray = reflection_ray(c, ray, hh);
+  cell_before(h, ray.dir, t.cx, t.cy, t.cz);
+  return tree_start(c, h, hh, ray.dir, t);
+}
+
+// GetRefractionRay (voxel.glsl:217-246) of a certified hit: the probes at point +- normal / 2
+// (:219-220) read the exact point's cells when the point is robust on the other axes (cert_start
+// checks it); total internal reflection turns it into the reflection ray, back before the face
+template <bool TEX>
+__device__ __forceinline__ bool tree_refraction(const Ctx& c, const Ray& ray, const CertResult& h, const Hit& hh,
+                                                TreeRay& t) {
+  const float eta = mat_refr(get_voxel(c, hh.point + hh.normal * 0.5f)) /
+                    mat_refr(get_voxel(c, hh.point - hh.normal * 0.5f));
+  const f3 rd = refract3(normalize3(ray.dir), hh.normal, eta);
+  const bool tir = rd.x == 0.0f && rd.y == 0.0f && rd.z == 0.0f;
+  if (tir ? !(c.refl_noise == 0.0f && zero_noise_exact(reflect3(ray.dir, hh.normal)))
+          : !(c.refr_noise == 0.0f && zero_noise_exact(rd)))
+    return false;
+  Counters kk;
+#pragma unroll
+  for (int q = 0; q < VRT_CNT_COUNT; ++q) kk.c[q] = 0;
+  t.ray = refraction_ray<TEX>(c, ray, hh, kk);
+  t.cx = h.cx;  // into the hit cell, or (total internal reflection) back before it
+  t.cy = h.cy;
+  t.cz = h.cz;
+  if ((comp(t.ray.dir, h.axis) > 0.0f) != (comp(ray.dir, h.axis) > 0.0f)) cell_before(h, ray.dir, t.cx, t.cy, t.cz);
+  return tree_start(c, h, hh, ray.dir, t);
+}
+
+// One ray of a certified tree: the colour update of `ray`'s walk outcome h, its children, then the
+// walk of the ray the reference pops next (ray, h updated). kTreeDone: the tree is complete (colour
+// final); kTreeUnsure: it cannot be certified (colour meaningless); kTreeNext: continue with ray, h.
+constexpr int kTreeNext = 0, kTreeDone = 1, kTreeUnsure = -1;
+template <int NL>
+__device__ __forceinline__ int tree_step(const Ctx& c, int max_refl, int max_transp, Ray& ray, CertResult& h,
+                                         f3& color, bool& pending, float4* __restrict__ lta,
+                                         float* __restrict__ ltb) {
+  // the sun vector opaque per ray, as in the exact path's bounce loop (trace_with_shadow): else
+  // the shadow walk's per-sun products are hoisted into VGPRs live across the whole tree and
+  // spilled on its entry
+  Ctx lc = c;
+  asm volatile("" : "+s"(lc.sun_n.x), "+s"(lc.sun_n.y), "+s"(lc.sun_n.z), "+s"(lc.sun_rcp.x),
+               "+s"(lc.sun_rcp.y), "+s"(lc.sun_rcp.z));
+  bool next = false;
+  TreeRay t;
+  CTRACE(c, 200, h.res, h.byte, h.axis, h.u, h.eu, ray.rdepth, ray.tdepth);
+  CTRACE(c, 201, ray.pos.x, ray.pos.y, ray.pos.z, ray.dir.x, ray.dir.y, ray.dir.z, ray.len);
+  CTRACE(c, 202, color.x, color.y, color.z, ray.energy, h.cx, h.cy, h.cz);
+  if (h.res == CERT_MISS) {
+    apply_sky_color(c, ray, color);
+  } else {
+    const Hit hh = cert_hit_record(ray, h);
+    if (!cert_shade_hit<false>(lc, ray, h, hh, color)) { CERT_DIAG(22); return kTreeUnsure; }
+    // children (:440-448): the reflection ray is pushed first, the refraction ray second and
+    // popped first; the stack (R + T + 1 entries) never fills with at most one ray waiting
+    const uint32_t m = mat_id(h.byte);
+    const bool pr = mat_reflective(m) && ray.rdepth < max_refl;
+    const bool pt = mat_transparent(m) && ray.tdepth < max_transp && get_color<false>(c, hh).w != 1.0f;
+    if (pr && pt) {
+      if (pending) { CERT_DIAG(18); return kTreeUnsure; }
+      TreeRay r;
+      if (!tree_reflection<false>(c, ray, h, hh, r)) { CERT_DIAG(19); return kTreeUnsure; }
+      tree_put<NL>(lta, ltb, r);
+      pending = true;
+      if (!tree_refraction<false>(c, ray, h, hh, t)) { CERT_DIAG(20); return kTreeUnsure; }
+      next = true;
+    } else if (pr) {
+      if (!tree_reflection<false>(c, ray, h, hh, t)) { CERT_DIAG(19); return kTreeUnsure; }
+      next = true;
+    } else if (pt) {
+      if (!tree_refraction<false>(c, ray, h, hh, t)) { CERT_DIAG(20); return kTreeUnsure; }
+      next = true;
+    }
+  }
+  if (!next) {
+    if (!pending) { CERT_DIAG(17); return kTreeDone; }
+    pending = false;
+    t = tree_get<NL>(lta, ltb);
+  }
+  ray = t.ray;
+  h = cert_march(c, ray, t.cx, t.cy, t.cz, t.e0, t.ed);
+  if (h.res == CERT_UNSURE) { CERT_DIAG(21); return kTreeUnsure; }
+  CERT_DIAG(23);
+  return kTreeNext;
+}
+
+// The bounce tree of a glass primary hit h0 of ray0 (fragment main, voxel.glsl:425-452) by
+// certified walks, colour folded in the reference's DFS order as TraceWithShadow does (:395-423):
+// each ray's RayMarch by cert_march, its hit shaded with a certified shadow (none for glass), a
+// miss with the sky colour. Colour-only (TEX false) frames. Returns false, colour untouched, when
+// any walk, start or direction could differ from the exact path's.
+// (Walking the primary ray through this loop too, one walk call site for every ray, made the
+// certified pass 3x slower: every pixel then carried the tree's registers; r06_s4.)
+// lta / ltb: this lane's LDS slot (tree_put; NL lanes per workgroup).
+template <int NL>
+__device__ __forceinline__ bool cert_tree(const Ctx& c, int max_refl, int max_transp, const Ray& ray0,
+                                          const CertResult& h0, f3& color_out, float4* __restrict__ lta,
+                                          float* __restrict__ ltb) {
+  f3 color = mk(0.0f, 0.0f, 0.0f);
+  Ray ray = ray0;
+  CertResult h = h0;
+  bool pending = false;  // a reflection ray waits in the LDS slot
+  CERT_DIAG(16);
+  for (;;) {
+    const int r = tree_step<NL>(c, max_refl, max_transp, ray, h, color, pending, lta, ltb);
+    if (r == kTreeUnsure) return false;
+    if (r == kTreeDone) break;
+  }
+  color_out = color;
+  return true;
+}
+
+// The exact walk's start cell from P along D (voxel.glsl:306-309: first planes d < 0 ? ceil(p - 1)
+// : floor(p + 1)); false when it lies outside the volume or a plane disagrees with the cell's.
+__device__ __forceinline__ bool exact_start_cell(const Ctx& c, const f3 P, const f3 D, int& cx, int& cy,
+                                                 int& cz) {
+  const int sx = D.x > 0.0f ? 1 : -1, sy = D.y > 0.0f ? 1 : -1, sz = D.z > 0.0f ? 1 : -1;
+  cx = sx > 0 ? int(__builtin_floorf(P.x)) : int(__builtin_ceilf(P.x)) - 1;
+  cy = sy > 0 ? int(__builtin_floorf(P.y)) : int(__builtin_ceilf(P.y)) - 1;
+  cz = sz > 0 ? int(__builtin_floorf(P.z)) : int(__builtin_ceilf(P.z)) - 1;
+  const float wpx = sx > 0 ? __builtin_floorf(P.x + 1.0f) : __builtin_ceilf(P.x - 1.0f);
+  const float wpy = sy > 0 ? __builtin_floorf(P.y + 1.0f) : __builtin_ceilf(P.y - 1.0f);
+  const float wpz = sz > 0 ? __builtin_floorf(P.z + 1.0f) : __builtin_ceilf(P.z - 1.0f);
+  const uint32_t n = uint32_t(c.n);
+  if (uint32_t(cx) >= n || uint32_t(cy) >= n || uint32_t(cz) >= n) return false;
+  return wpx == float(cx + (sx > 0)) && wpy == float(cy + (sy > 0)) && wpz == float(cz + (sz > 0));
+}
+
+// Cells the exact walk samples behind its start cell. A start coordinate P_a that is an integer k
+// with D_a < 0 (a shadow or secondary ray from an exact hit point on its face plane) makes the
+// start cell k - 1 on axis a, but until cur_a = P_a + s D_a rounds off k the exact walk samples
+// layer k — beyond the plane — at every crossing of another axis (r02 s18: a shadow ray from
+// (33.000008, 127, 37.02) going -x, -y sampled the panel voxel (32, 127, 37) at its x crossing
+// 8.5e-6 after the start; the certified walk had jumped that crossing). The certified walk cannot
+// see those cells, so they are checked here: every cell of layer k the walk may enter across an
+// axis crossed within 2 ulp(k) / |D_a| (+1e-5) of the start must be a non-event, else unsure.
+template <bool SHADOW>
+__device__ __forceinline__ bool start_layers_clear(const Ctx& c, const f3 P, const f3 D, int cx, int cy,
+                                                   int cz, uint32_t medium) {
+  const float p[3] = {P.x, P.y, P.z}, d[3] = {D.x, D.y, D.z};
+  const int cell[3] = {cx, cy, cz};
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    if (!(d[a] < 0.0f) || p[a] != __builtin_floorf(p[a])) continue;
+    const float off = (0x1p-22f * __builtin_fmaxf(__builtin_fabsf(p[a]), 1.0f) + 1e-5f) / __builtin_fabsf(d[a]);
+    // two crossings of one axis b in layer k (a nearly parallel D_a keeps cur_a on k: a
+    // straight-down lattice camera's ray at x = 64 with D_x = -2.2e-8 read plane N's GL_REPEAT
+    // copy for 170 units) need off >= 1 / |D_b| >= 1: more cells than checked here, unsure
+    if (off >= 1.0f) return false;
+    int q[3] = {cell[0], cell[1], cell[2]};
+    q[a] += 1;  // layer k
+    bool early[3] = {false, false, false};
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+      if (b == a) continue;
+      const float plane = float(cell[b] + (d[b] > 0.0f ? 1 : 0));
+      early[b] = (plane - p[b]) / d[b] < off;  // first crossing of axis b
+    }
+    const int b1 = a == 0 ? 1 : 0, b2 = a == 2 ? 1 : 2;
+    const int s1 = d[b1] > 0.0f ? 1 : -1, s2 = d[b2] > 0.0f ? 1 : -1;
+    // shadow walks: the exact walk may cross b in layer k and so never sample the start layer's
+    // cell across b, which the certified walk reaches by that crossing and, if it blocks,
+    // reports as a hit "whichever way the walk goes" (a straight-down lattice camera's shadow
+    // from x = 33.0 going -x sampled (33, 30, 2) at its z crossing and never the solid (32, 30,
+    // 2)): unsure whenever a crossing falls in the sliver
+    if (SHADOW && (early[b1] || early[b2])) return false;
+    int r[3];
+    if (early[b1]) {
+      r[0] = q[0]; r[1] = q[1]; r[2] = q[2]; r[b1] += s1;
+      if (cert_event<SHADOW>(alt_byte(c, r[0], r[1], r[2], 0u), medium)) return false;
+    }
+    if (early[b2]) {
+      r[0] = q[0]; r[1] = q[1]; r[2] = q[2]; r[b2] += s2;
+      if (cert_event<SHADOW>(alt_byte(c, r[0], r[1], r[2], 0u), medium)) return false;
+    }
+    if (early[b1] && early[b2]) {
+      r[0] = q[0]; r[1] = q[1]; r[2] = q[2]; r[b1] += s1; r[b2] += s2;
+      if (cert_event<SHADOW>(alt_byte(c, r[0], r[1], r[2], 0u), medium)) return false;
+    }
+  }
+  return true;
+}
+
+// The shadow bit of an exact hit h by a certified walk: the shadow ray starts at the exact hit
+// point h.point with len h.len (GetShadowRay, :191-201), so its start is known exactly, as a
+// primary ray's is (e0 = 0, the exact walk's own start cell). 1 blocked, 0 lit, -1 unsure.
+__device__ __forceinline__ int cert_shadow_exact(const Ctx& c, const Hit& h) {
+  const f3 S = c.sun_n;
+  int cx, cy, cz;
+  if (!fast_path_ok(S) || !exact_start_cell(c, h.point, S, cx, cy, cz)) return -1;
+  if (!start_layers_clear<true>(c, h.point, S, cx, cy, cz, 0u)) return -1;
+  const CertResult s = cert_walk<true>(c, h.point, S, c.sun_rcp, c.max_len - h.len, cx, cy, cz, 0.0f,
+                                       mk(0.0f, 0.0f, 0.0f), h.len, 0u);
+  return s.res == CERT_UNSURE ? -1 : (s.res == CERT_HIT ? 1 : 0);
+}
+
+// An air segment of a bounce-stack ray by a certified walk from the exact point ray.pos (len
+// ray.len) in cell (cx, cy, cz); ed: per-axis crossing-order uncertainty of the exact walk's
+// planes. In an air medium every event is a hit (:353), and a non-glass hit spawns no rays
+// (:440-448). true (colour updated as TraceWithShadow's, :395-423): a miss, or a non-glass hit
+// whose shadow certifies. false (colour untouched): the exact march goes on.
+__device__ __forceinline__ bool cert_air_segment(const Ctx& c, const Ray& ray, int cx, int cy, int cz,
+                                                 const f3 ed, f3& color) {
+  const f3 D = ray.dir;
+  const f3 rcp = mk(__builtin_amdgcn_rcpf(D.x), __builtin_amdgcn_rcpf(D.y), __builtin_amdgcn_rcpf(D.z));
+  const CertResult h = cert_walk<false>(c, ray.pos, D, rcp, c.max_len - ray.len, cx, cy, cz, 0.0f, ed,
+                                        ray.len, 0u);
+  if (h.res == CERT_UNSURE) return false;
+  if (h.res == CERT_MISS) {
+    apply_sky_color(c, ray, color);
+    return true;
+  }
+  if (mat_id(h.byte) == 2u) return false;
+  return cert_shade_hit(c, ray, h, cert_hit_record(ray, h), color);
+}
+
+// A secondary ray from an exact origin (the reflection or refraction ray of an exact hit) in air:
+// its walk certifies as a primary's does
+__device__ __forceinline__ bool cert_secondary(const Ctx& c, const Ray& ray, f3& color) {
+  int cx, cy, cz;
+  if (ray.voxel != 0u || !fast_path_ok(ray.dir) || !exact_start_cell(c, ray.pos, ray.dir, cx, cy, cz) ||
+      !start_layers_clear<false>(c, ray.pos, ray.dir, cx, cy, cz, 0u))
+    return false;
+  return cert_air_segment(c, ray, cx, cy, cz, mk(0.0f, 0.0f, 0.0f), color);
+}
+
+// The rest of a march after an in-volume refraction into air at the exact crossing w.cur of axis
+// fa (march, :357-380): the exact walk goes on from pos = cur, len0 = w.len, with the first
+// planes initial_t's on the other axes and cur_fa + sign on axis fa. That plane lies within
+// delta = |(cur_fa + sign) - (k + sign)| of the lattice plane (k = rint(cur_fa)), and every later
+// axis-fa plane of the walk (cur_fa + sign at each crossing) keeps that offset: the certified walk
+// starts in the cell beyond k and takes delta |1/d_fa| (doubled) as that axis's crossing-order
+// uncertainty. The step cap (VRT_MAX_STEPS per march) must be out of reach: <= 3N + 4 more steps.
+__device__ __forceinline__ bool cert_continuation(const Ctx& c, const Ray& ray, const WalkState& w, int fa,
+                                                  f3& color) {
+  const f3 D = ray.dir, P = ray.pos;
+  if (!fast_path_ok(D) || w.it + 3u * uint32_t(c.n) + 16u > uint32_t(VRT_MAX_STEPS)) return false;
+  int cx, cy, cz;
+  const float pa = comp(P, fa), da = comp(D, fa);
+  const float k = __builtin_rintf(pa);
+  const float sa = da > 0.0f ? 1.0f : -1.0f;
+  const float delta = __builtin_fabsf((pa + sa) - (k + sa));
+  if (!(delta < 1e-3f)) return false;
+  // the other axes as a fresh walk's start; axis fa replaced below
+  {
+    const int sx = D.x > 0.0f ? 1 : -1, sy = D.y > 0.0f ? 1 : -1, sz = D.z > 0.0f ? 1 : -1;
+    cx = sx > 0 ? int(__builtin_floorf(P.x)) : int(__builtin_ceilf(P.x)) - 1;
+    cy = sy > 0 ? int(__builtin_floorf(P.y)) : int(__builtin_ceilf(P.y)) - 1;
+    cz = sz > 0 ? int(__builtin_floorf(P.z)) : int(__builtin_ceilf(P.z)) - 1;
+    const float wpx = sx > 0 ? __builtin_floorf(P.x + 1.0f) : __builtin_ceilf(P.x - 1.0f);
+    const float wpy = sy > 0 ? __builtin_floorf(P.y + 1.0f) : __builtin_ceilf(P.y - 1.0f);
+    const float wpz = sz > 0 ? __builtin_floorf(P.z + 1.0f) : __builtin_ceilf(P.z - 1.0f);
+    if ((fa != 0 && wpx != float(cx + (sx > 0))) || (fa != 1 && wpy != float(cy + (sy > 0))) ||
+        (fa != 2 && wpz != float(cz + (sz > 0))))
+      return false;
+    const int ka = int(k) - (da > 0.0f ? 0 : 1);
+    if (fa == 0) cx = ka;
+    else if (fa == 1) cy = ka;
+    else cz = ka;
+  }
+  const uint32_t n = uint32_t(c.n);
+  if (uint32_t(cx) >= n || uint32_t(cy) >= n || uint32_t(cz) >= n) return false;
+  // the start cell lies beyond plane k on axis fa, but P_fa may lie before it (by up to delta) or
+  // on it: until cur_fa = P_fa + s D_fa is past k, the exact walk samples the layer before k at
+  // every crossing of another axis (as start_layers_clear's layer k for a start on a plane), which
+  // the certified walk does not see (a glass cube's face voxel beside the refraction point,
+  // sampled 3.7e-6 after the start, made a lattice camera's pixel differ before this test):
+  // unsure when another axis is crossed that early. By the hardware reciprocal (<= 1 ulp) against
+  // a bound widened past its error: never fewer cases than the exact quotients would give.
+  {
+    const float before = __builtin_fmaxf((k - pa) * sa, 0.0f);
+    const float off = (before + 0x1p-22f * __builtin_fmaxf(__builtin_fabsf(pa), 1.0f) + 1e-5f) *
+                      __builtin_fabsf(__builtin_amdgcn_rcpf(da)) * 1.00002f;
+    const float tx = fa == 0 ? off : (float(cx + (D.x > 0.0f ? 1 : 0)) - P.x) * __builtin_amdgcn_rcpf(D.x);
+    const float ty = fa == 1 ? off : (float(cy + (D.y > 0.0f ? 1 : 0)) - P.y) * __builtin_amdgcn_rcpf(D.y);
+    const float tz = fa == 2 ? off : (float(cz + (D.z > 0.0f ? 1 : 0)) - P.z) * __builtin_amdgcn_rcpf(D.z);
+    if (__builtin_fminf(tx, __builtin_fminf(ty, tz)) < off) return false;
+  }
+  f3 ed = mk(0.0f, 0.0f, 0.0f);
+  set_comp(ed, fa, 2.0f * delta * __builtin_fabsf(__builtin_amdgcn_rcpf(da)) + 1e-6f);
+  return cert_air_segment(c, ray, cx, cy, cz, ed, color);
+}
+
+// RayMarch + TraceWithShadow of a bounce-stack ray (stats-free, colour-only) with its air
+// segments — the whole ray from its exact origin, or the rest after an in-volume refraction into
+// air — settled by certified walks where they can be (settled: colour updated, no secondary
+// rays); the exact march (as march()) otherwise.
+// (Out of line it costs C2-C4 +45 %, profiles/r01_v69_ab_noinline_w6.log.)
+__device__ __forceinline__ Hit march_cert(const Ctx& c, Ray& ray, f3& color, bool& settled, Counters& k,
+                          uint32_t& steps, uint32_t& flags) {
+  Hit h;
+  h.found = false;
+  h.vidx = -1;
+  h.len = 0.0f;
+  h.voxel = 0;
+  h.point = mk(0.0f, 0.0f, 0.0f);
+  h.normal = h.point;
+  h.axis = 0;
+  settled = cert_secondary(c, ray, color);
+  if (settled) return h;
+  WalkState w;
+  walk_init(w, ray);
+  uint32_t medium = ray.voxel;
+  int internal = 0;
+  for (;;) {
+    int axis;
+    int32_t vidx;
+    uint32_t v;
+    const int r = walk_ray<false>(c, ray.pos, ray.dir, ray.len, medium, w, axis, vidx, v);
+    if (r != WALK_EVENT) break;
+    f3 normal = mk(0.0f, 0.0f, 0.0f);
+    set_comp(normal, axis, -gsign(comp(ray.dir, axis)));
+    if (v != 0u) {
+      h.found = true;
+      h.voxel = v;
+      h.vidx = vidx;
+      h.point = w.cur;
+      h.len = w.len;
+      h.normal = normal;
+      h.axis = axis;
+      break;
+    }
+    Hit e;
+    e.found = true;
+    e.voxel = 0;
+    e.vidx = vidx;
+    e.point = w.cur;
+    e.len = w.len;
+    e.normal = normal;
+    e.axis = axis;
+    const f3 old_dir = ray.dir;
+    ray = refraction_ray<false>(c, ray, e, k);
+    ray.tdepth--;
+    if (ray.voxel == medium) {
+      internal++;
+      if (internal > 10) {
+        ray.dir = old_dir;
+        ray.voxel = 0;
+      }
+    }
+    medium = ray.voxel;
+    w.t = initial_t(ray.dir, w.cur, ray.pos);
+    const f3 step = sign3(ray.dir);
+    const float q = ((comp(w.cur, axis) + comp(step, axis)) - comp(ray.pos, axis)) /
+                        comp(ray.dir, axis) - (w.len - ray.len);
+    set_comp(w.t, axis, q);
+    if (medium == 0u && cert_continuation(c, ray, w, axis, color)) {
+      settled = true;
+      return h;
+    }
+  }
+  return h;
+}
+
+// The whole pixel by certified walks, when it can be certified: a primary miss, or a non-glass
+// primary hit with its shadow. The pixel's colour starts black (voxel.glsl:428); color_out is
+// written only when the pixel certifies. false when any walk or any derived value could differ
+// from the exact path's, or the hit is glass (its secondary rays start at the exact hit point):
+// the pixel then takes the exact path.
+// Textured mode: the texel GetColor (voxel.glsl:174-182) reads at the exact hit point, from the
+// certified hit. The exact hit point is currentPos of the exact walk's hit step; on each face axis
+// it lies within delta = eu |D_b| + the roundings of both points' pos + s dir of the certified
+// point (eu bounds the exact walk's parameter there, cert_gamma). get_color's texel index is a
+// composition of correctly rounded monotone operations of the coordinate (frac by floor, + texX,
+// x ts, / S, floor(. x S)), so if both ends of [p - delta, p + delta] lie in the same voxel and give
+// the same texel, every point between does: the exact texel is that one. false: unsure.
+__device__ __forceinline__ bool texel_pair(const Ctx& c, float p, float d, uint32_t slot, bool flip, uint32_t& t) {
+  const float lo = p - d, hi = p + d;
+  if (__builtin_floorf(lo) != __builtin_floorf(hi)) return false;
+  auto idx = [&](float q) {
+    const float f = q - floorf(q);
+    if (!flip) {  // tx = ((fx + texX) * ts) / S, u = tx
+      const float u = ((f + float(slot)) * c.atlas_fts) / c.atlas_fs;
+      return cvt_flr(u * c.atlas_fs) & c.atlas_mask;
+    }
+    const float ty = (((1.0f - f) + float(slot)) * c.atlas_fts) / c.atlas_fs;  // v = 1 - ty
+    return cvt_flr((1.0f - ty) * c.atlas_fs) & c.atlas_mask;
+  };
+  t = idx(lo);
+  return t == idx(hi);
+}
+
+__device__ __forceinline__ bool cert_texel(const Ctx& c, const Ray& ray, const CertResult& h, const Hit& hh,
+                                           float4& col) {
+  const uint32_t m = mat_id(h.byte);
+  const float px = hh.axis == 0 ? hh.point.z : hh.point.x;  // intersectionAxis[a][1]
+  const float py = hh.axis == 2 ? hh.point.y : (hh.axis == 1 ? hh.point.z : hh.point.y);  // [a][2]
+  const float dx = hh.axis == 0 ? ray.dir.z : ray.dir.x;
+  const float dy = hh.axis == 2 ? ray.dir.y : (hh.axis == 1 ? ray.dir.z : ray.dir.y);
+  const float px0 = hh.axis == 0 ? ray.pos.z : ray.pos.x;
+  const float py0 = hh.axis == 2 ? ray.pos.y : (hh.axis == 1 ? ray.pos.z : ray.pos.y);
+  // eu along the ray, plus 2 ulp-scale roundings of each point's P + s D (both points), doubled
+  const float ex = h.eu * __builtin_fabsf(dx) +
+                   0x1p-21f * (__builtin_fabsf(px0) + __builtin_fabsf(h.u * dx) + __builtin_fabsf(px) + 1.0f);
+  const float ey = h.eu * __builtin_fabsf(dy) +
+                   0x1p-21f * (__builtin_fabsf(py0) + __builtin_fabsf(h.u * dy) + __builtin_fabsf(py) + 1.0f);
+  uint32_t i, j;
+  if (!texel_pair(c, px, ex, mat_tex_x(m), false, i) || !texel_pair(c, py, ey, mat_tex_y(m), true, j)) return false;
+  const uint32_t t = c.atlas[j * (c.atlas_mask + 1u) + i];
+  col = make_float4(float(t & 0xFFu) / 255.0f, float((t >> 8) & 0xFFu) / 255.0f,
+                    float((t >> 16) & 0xFFu) / 255.0f, float(t >> 24) / 255.0f);
+  return true;
+}
+
+// TREE (colour-only): a glass primary hit's bounce tree by certified walks too (cert_tree; ltb and c.ax its
+// LDS slot), instead of leaving the whole pixel to the exact path.
+// us_out: the primary walk's certified prefix (CertResult::us) for the exact path, -1 if none.
+template <bool TEX = false, bool TREE = false, int NL = kWgThreads>
+__device__ __forceinline__ bool cert_pixel(const Ctx& c, const Ray& ray0, f3& color_out, int max_refl = 0,
+                                           int max_transp = 0, float* __restrict__ ltb = nullptr,
+                                           float* us_out = nullptr) {
+  const f3 P = ray0.pos, D = ray0.dir;
+  if (!fast_path_ok(D)) { CERT_DIAG(0); return false; }
+  int cx, cy, cz;
+  if (!exact_start_cell(c, P, D, cx, cy, cz) || !start_layers_clear<false>(c, P, D, cx, cy, cz, 0u)) {
+    CERT_DIAG(0);
+    return false;
+  }
+  // hardware reciprocals (<= 1 ulp): the certified walk only needs its own error bounded
+  const f3 rcp = mk(__builtin_amdgcn_rcpf(D.x), __builtin_amdgcn_rcpf(D.y), __builtin_amdgcn_rcpf(D.z));
+  CertResult h = cert_walk<false>(c, P, D, rcp, c.max_len - ray0.len, cx, cy, cz, 0.0f,
+                                  mk(0.0f, 0.0f, 0.0f), 0.0f, 0u);
+  if (us_out) *us_out = h.us;
+  CERT_DIAG_ONLY(cert_diag_iters(10, h.iters);)
+  if (h.res == CERT_UNSURE) { CERT_DIAG(1); return false; }
+  f3 color = mk(0.0f, 0.0f, 0.0f);
+  if (h.res == CERT_MISS) {
+    CERT_DIAG(2);
+    apply_sky_color(c, ray0, color);
+    color_out = color;
+    return true;
+  }
+  if (mat_id(h.byte) == 2u) {  // only glass spawns secondary rays (:440-448)
+    CERT_DIAG(3);
+    if constexpr (TREE && !TEX) return cert_tree<NL>(c, max_refl, max_transp, ray0, h, color_out, c.ax, ltb);
+    return false;
+  }
+  const Hit hh = cert_hit_record(ray0, h);
+  float4 col = float4();
+  if (TEX && !cert_texel(c, ray0, h, hh, col)) return false;
+  if (!cert_shade_hit<TEX>(c, ray0, h, hh, color, col)) return false;
+  color_out = color;
+  return true;
+}
+
+}  // namespace vrt
+
+#endif  // VRT_CERT_H

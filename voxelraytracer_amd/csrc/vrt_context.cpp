@@ -54,10 +54,6 @@ uint32_t defer_seg_tiles(uint32_t tiles, uint32_t tiles_x) {
 size_t defer_words(uint32_t tiles, uint32_t tiles_x) {
   return vrt::kDeferHdr + size_t(vrt::kOrdClasses) * defer_seg_tiles(tiles, tiles_x) * vrt::kWgThreads;
 }
-#if (defined(VRT_DEV_NOQUERY) || defined(VRT_DEV_NOCONSUME) || defined(VRT_DEV_NOCSWAIT)) && \
-    !defined(VRT_DIAGNOSTIC_BUILD)
-#error "VRT_DEV_* are diagnostic knobs of make variant builds"
-#endif
 // Filtered frames rotate through kRing buffers: frame f reads ring[(f-1) % kRing] (the temporal
 // history) and writes ring[f % kRing]. A device-output frame (vrt_render_frame_device) is handed
 // to the caller as its ring buffer and stays valid until the fourth later call, with no copy. Eight
@@ -546,12 +542,12 @@ OrderSlot* launch_state_begin(const vrt_ctx* ctx, Shard& s, vrt::KArgs& a, hipSt
   // the tile order only where it pays: glass in the volume (without it the order gains nothing:
   // C2 ±0, C4 +5 %, profiles/r02_s14_tileorder) and certified pixels (glass-heavy volumes, where
   // every tile is heavy, keep dispatch order: C1 +3.4 %)
-  // Nor for launches below one dispatch round of waves (VRT_ORD_MIN_ROUNDS): all of their tiles are
+  // Nor for launches below one dispatch round of waves (kOrdMinRounds): all of their tiles are
   // resident at once, so an order only costs its list reads and bookkeeping (C3's 8-way bands
   // in flight: rank 7 0.0078 -> 0.0072, rank 6 0.0127 -> 0.0105 ms per frame, profiles/r05_s14)
   const bool order = !defer && ctx->tile_order != 0 && !a.textured && a.cert == 2 && s.has_glass &&
                      (ctx->tile_order == 2 ||
-                      a.tiles * uint32_t(vrt::kWgWaves) >= uint32_t(VRT_ORD_MIN_ROUNDS) * s.wave_slots);
+                      a.tiles * uint32_t(vrt::kWgWaves) >= vrt::kOrdMinRounds * s.wave_slots);
   if (!defer && !order) return nullptr;
   OrderSlot* slot = acquire_slot(s, a, st);
   if (!slot) return nullptr;
@@ -579,7 +575,7 @@ OrderSlot* launch_state_begin(const vrt_ctx* ctx, Shard& s, vrt::KArgs& a, hipSt
     a.defer_seg = defer_seg_tiles(a.tiles, a.tiles_x) * uint32_t(vrt::kWgThreads);
     // bands of under 4 rounds: the exact pass's latency follows a short certified pass
     a.exact_fat = !a.textured && (lone || a.tiles * uint32_t(vrt::kWgWaves) < 4u * s.wave_slots) ? 1 : 0;
-    if (VRT_EXACT_GRID_ADAPT && !a.exact_fat) {
+    if (!a.exact_fat) {
       const uint32_t div = a.textured ? vrt::kDeferGridDiv : vrt::kDeferGridDivColor;  // launch_render's
       // the grid from an earlier frame's batch count on this slot (frames in flight: a few frames
       // old) plus a margin; a larger frame loops its workgroups over the rest. Idle workgroups
@@ -759,6 +755,10 @@ int ensure_history(vrt_ctx* ctx, int32_t w, int32_t h) {
       VRT_HIP(ctx, hipMemset(s.d_rawbuf[r], 0, pixels * 4));
       s.band_read_valid[r] = false;
     }
+    // hipMemset of device memory does not wait for the fill, and the lane streams are non-blocking
+    // (not ordered after the null stream): without this wait a fill could land after the first
+    // frame's pixels (black rows in a fresh context's first 4K frame, now and then)
+    VRT_HIP(ctx, hipDeviceSynchronize());
     for (int l = 0; l < kLanes; ++l) s.lane_parts[l] = 0;
     for (int r = 0; r < kRing; ++r) s.slot_reader[r] = 0;
   }
@@ -801,11 +801,9 @@ int wait_lane(vrt_ctx* ctx, Shard& s, int l, hipStream_t st) {
 //  - a frame read this slot as its history: its lane's last launches (WAR; that lane's later
 //    frames end after it);
 //  - a device-output gather of frame fk-4 read this slot: its gather stream;
-//  - wait_consumed: the caller's consumption of the device-output frame in this slot.
 // timing: device timestamps of every launch (vrt_stats.kernel_ms; synchronous calls only).
 int launch_frame(vrt_ctx* ctx, const vrt_camera* cam, const vrt_params* p, float alpha, bool rgba8,
-                 bool hits, bool counting, bool timing, bool overlap, hipEvent_t wait_consumed = nullptr,
-                 bool one_part = false) {
+                 bool hits, bool counting, bool timing, bool overlap, bool one_part = false) {
   const int32_t k = int32_t(ctx->sh.size()), w = cam->width, h = cam->height;
   const uint64_t f = ctx->fk;
   const int g = int(f % kLanes), slot = int(f % kRing), pslot = int((f + kRing - 1) % kRing);
@@ -841,7 +839,6 @@ int launch_frame(vrt_ctx* ctx, const vrt_camera* cam, const vrt_params* p, float
       if (rgba8 && s.slot_reader[slot] > 0 && (st = wait_lane(ctx, s, s.slot_reader[slot] - 1, sq)) != VRT_OK)
         return st;
       if (rgba8 && s.band_read_valid[slot]) VRT_HIP(ctx, hipStreamWaitEvent(sq, s.ev_band_read[slot], 0));
-      if (wait_consumed) VRT_HIP(ctx, hipStreamWaitEvent(sq, wait_consumed, 0));
     }
     if (rgba8) s.band_read_valid[slot] = false;
     if (counting)
@@ -966,9 +963,8 @@ int stage_bands(vrt_ctx* ctx, int g, int32_t w, int32_t h, const void* const* ba
 // Several devices (or the one-device RCCL rehearsal): frame f's bands (launched on lane g) to the
 // first device — ncclGather over xGMI on every device's gather stream, or device-to-device copies
 // when a device repeats — then placed into their rows of d_frames[slot] on the first device's
-// gather stream (after `reuse`, the caller's consumption of that buffer, when given); ev_gathered
-// marks the assembled frame.
-int gather_frame(vrt_ctx* ctx, int32_t w, int32_t h, int slot, int g, hipEvent_t reuse, const uint32_t** d_frame) {
+// gather stream; ev_gathered marks the assembled frame.
+int gather_frame(vrt_ctx* ctx, int32_t w, int32_t h, int slot, int g, const uint32_t** d_frame) {
   const int32_t k = int32_t(ctx->sh.size());
   Shard& root = ctx->sh[0];
   int st;
@@ -1017,7 +1013,6 @@ int gather_frame(vrt_ctx* ctx, int32_t w, int32_t h, int slot, int g, hipEvent_t
     for (int32_t j = 0; j < k; ++j) src[j] = ctx->sh[j].d_ring[slot];
   }
   VRT_HIP(ctx, hipSetDevice(root.device));
-  if (reuse) VRT_HIP(ctx, hipStreamWaitEvent(root.gs, reuse, 0));
   uint32_t* out = ctx->d_frames[slot];
   if (ctx->distinct) {  // the gathered bands, cap rows apart, into their frame rows: one kernel
     vrt::launch_assemble_blocks(ctx->d_gather, uint64_t(cap) * uint64_t(w), k, k > 1 ? kFrameRowBlockSh : 0, w, h,
@@ -1683,14 +1678,14 @@ int vrt_render_frame_device(vrt_ctx* ctx, const vrt_camera* cam, const vrt_param
         ctx->consumed_valid[rs] = false;
       }
     }
-    if ((st = launch_frame(ctx, cam, p, alpha, true, false, counting, stats != nullptr, true, nullptr, true)) !=
+    if ((st = launch_frame(ctx, cam, p, alpha, true, false, counting, stats != nullptr, true, true)) !=
         VRT_OK)
       return st;
     if (k == 1 && !ctx->coll1) {
       ctx->frame_stream = root.ls[g][0];
       *d_frame = root.d_ring[slot];
     } else {
-      if ((st = gather_frame(ctx, w, h, slot, g, nullptr, d_frame)) != VRT_OK) return st;
+      if ((st = gather_frame(ctx, w, h, slot, g, d_frame)) != VRT_OK) return st;
       ctx->frame_stream = root.gs;
     }
     VRT_HIP(ctx, hipSetDevice(root.device));
@@ -1709,30 +1704,21 @@ int vrt_render_frame_device(vrt_ctx* ctx, const vrt_camera* cam, const vrt_param
   // (the caller's stream is more than kRing - 1 frames behind): a swapchain's back-pressure, with
   // no ordering packet on the GPU. (Waiting for it on the lane's stream cost 0.016 ms per C3 frame:
   // the cross-queue wait packets stalled the lanes; profiles/r03_s14; the one-off script is in git history.)
-  hipEvent_t reuse = nullptr;
   if (f >= kRing) {
     const int rs = int((f - kRing + 1) % kRing);
-#if defined(VRT_DEV_NOQUERY)  // diagnostic builds: the wait on the GPU (the r03 s13 scheme) / none (unsafe)
-    if (ctx->consumed_valid[rs]) reuse = ctx->ev_consumed[rs];
-#elif defined(VRT_DEV_NOCONSUME)
-    (void)rs;
-#else
     if (ctx->consumed_valid[rs] && hipEventQuery(ctx->ev_consumed[rs]) != hipSuccess)
       VRT_HIP(ctx, hipEventSynchronize(ctx->ev_consumed[rs]));
-#endif
   }
   if (k == 1 && !ctx->coll1) {
     // one device: the frame is rendered straight into the ring slot handed to the caller; up to
     // kLanes frames in flight (u_Alpha = 1: independent frames)
-    if ((st = launch_frame(ctx, cam, p, alpha, true, false, counting, stats != nullptr, true, reuse)) != VRT_OK)
+    if ((st = launch_frame(ctx, cam, p, alpha, true, false, counting, stats != nullptr, true)) != VRT_OK)
       return st;
-#ifndef VRT_DEV_NOCSWAIT  // diagnostic builds only: the caller's stream not ordered after the frame (unsafe)
     for (int q = 0; q < root.lane_parts[g]; ++q) VRT_HIP(ctx, hipStreamWaitEvent(cs, root.ev_done[g][q], 0));
-#endif
     *d_frame = root.d_ring[slot];
   } else {
     if ((st = launch_frame(ctx, cam, p, alpha, true, false, counting, stats != nullptr, true)) != VRT_OK) return st;
-    if ((st = gather_frame(ctx, w, h, slot, g, reuse, d_frame)) != VRT_OK) return st;
+    if ((st = gather_frame(ctx, w, h, slot, g, d_frame)) != VRT_OK) return st;
     VRT_HIP(ctx, hipSetDevice(root.device));
     VRT_HIP(ctx, hipStreamWaitEvent(cs, ctx->ev_gathered, 0));
   }

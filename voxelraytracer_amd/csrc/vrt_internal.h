@@ -1,4 +1,4 @@
-// vrt_internal.h — the interface between the kernels (vrt_render.hip) and the C-ABI context
+// vrt_internal.h — the interface between the kernels (vrt_render.hip and its headers) and the C-ABI context
 // (vrt_context.cpp). Not installed; include/vrt.h is the public boundary.
 #ifndef VRT_INTERNAL_H
 #define VRT_INTERNAL_H
@@ -8,6 +8,7 @@
 #include <cstdint>
 
 #include "vrt.h"
+#include "vrt_tuning.h"
 
 namespace vrt {
 
@@ -60,8 +61,8 @@ struct KArgs {
   uint32_t* defer;
   uint32_t defer_e, defer_seg;
   int32_t exact_fat;  // the exact pass's short-band instance (colour-only bands of < 4 rounds of waves, lone frames)
-  // adaptive exact-pass grid (VRT_EXACT_GRID_ADAPT): workgroups of this launch's exact pass (0: the
-  // tiles-based default) and the slot's host-mapped word its workgroup 0 stores the batch count in
+  // adaptive exact-pass grid: workgroups of this launch's exact pass (0: the tiles-based default)
+  // and the slot's host-mapped word its workgroup 0 stores the batch count in
   uint32_t exact_grid;
   uint32_t* batches_out;
   // frame batches (vrt_render_temporal_batch_async, alpha 1): `nframes` frames of the same band in
@@ -77,26 +78,7 @@ struct KArgs {
   } fb[7];
 };
 constexpr int kMaxBatch = 8;  // frames per launch (1 + the fb entries)
-#if defined(VRT_EXACT_GRID_ADAPT) && !defined(VRT_DIAGNOSTIC_BUILD)
-#error "VRT_EXACT_GRID_ADAPT is an A/B knob of make variant builds"
-#endif
-#ifndef VRT_EXACT_GRID_ADAPT
-#define VRT_EXACT_GRID_ADAPT 1
-#endif
-
-// Waves per workgroup, each rendering an 8x8 pixel tile. Two (a 16x8 tile): a finished
-// workgroup frees its slots two waves at a time, so the dispatcher refills them sooner than with
-// four-wave 16x16 workgroups (C3 -4.4 %, C2 -2.8 %, C4 -8.1 % per frame; one wave per workgroup:
-// C3 -1.7 %, profiles/r02_s06). Images are identical at 1, 2 and 4 (A/B builds only: make variant).
-#if defined(VRT_WG_WAVES) && !defined(VRT_DIAGNOSTIC_BUILD)
-#error "VRT_WG_WAVES is an A/B knob of make variant builds"
-#endif
-#ifndef VRT_WG_WAVES
-#define VRT_WG_WAVES 2
-#endif
-constexpr int kWgWaves = VRT_WG_WAVES;
-static_assert(kWgWaves == 1 || kWgWaves == 2 || kWgWaves == 4, "1, 2 or 4 waves per workgroup");
-constexpr int kWgThreads = 64 * kWgWaves;
+constexpr int kWgThreads = 64 * kWgWaves;  // kWgWaves: vrt_tuning.h
 constexpr int kTileW = kWgWaves >= 2 ? 16 : 8;  // a workgroup's pixel tile: 16x16, 16x8 or 8x8
 constexpr int kTileH = kWgWaves == 4 ? 16 : 8;
 constexpr int kMaxStack = 17;               // bounce-stack entries: max_reflections + max_transparencies + 1
@@ -104,42 +86,12 @@ constexpr int kCntReplicas = 256;           // counter replicas (per-wave atomic
 constexpr uint32_t kOrdClasses = 8;         // tile-order lists: tile % 8 (the XCD of its slot)
 constexpr uint32_t kOrdCtrStride = 64;      // words between list counters (one 256-byte line each)
 constexpr uint32_t kOrdHdr = 3 * kOrdClasses * kOrdCtrStride;  // tile-order buffer header: 3 counter sets
-#if defined(VRT_ORD_DIV) && !defined(VRT_DIAGNOSTIC_BUILD)
-#error "VRT_ORD_DIV is an A/B knob of make variant builds"
-#endif
-#ifndef VRT_ORD_DIV
-#define VRT_ORD_DIV 4
-#endif
-// first-pass slots per class of a tile-order launch: tiles / (8 VRT_ORD_DIV), i.e. up to a quarter of
-// the tiles in the heavy-first pass (C3: ~1600 of a part launch's 8160 tiles are heavy)
+// first-pass slots per class of a tile-order launch (kOrdDiv, vrt_tuning.h)
 __host__ __device__ inline uint32_t ord_q_for(uint32_t tiles) {
-  return (tiles + kOrdClasses * VRT_ORD_DIV - 1u) / (kOrdClasses * VRT_ORD_DIV);
+  return (tiles + kOrdClasses * kOrdDiv - 1u) / (kOrdClasses * kOrdDiv);
 }
-#if defined(VRT_ORD_MIN_ROUNDS) && !defined(VRT_DIAGNOSTIC_BUILD)
-#error "VRT_ORD_MIN_ROUNDS is an A/B knob of make variant builds"
-#endif
-#ifndef VRT_ORD_MIN_ROUNDS  // dispatch rounds of waves from which an in-lane launch takes the tile order
-#define VRT_ORD_MIN_ROUNDS 1
-#endif
 constexpr uint32_t kDeferHdr = 4 * kOrdClasses * kOrdCtrStride;  // deferred-pass slot header: 2 kinds x 2 sets
 constexpr uint32_t kDeferDense = 32;        // deferred pixels from which a wave keeps its own exact-pass batch
-#if defined(VRT_DEFER_GRID_DIV) && !defined(VRT_DIAGNOSTIC_BUILD)
-#error "VRT_DEFER_GRID_DIV is an A/B knob of make variant builds"
-#endif
-#ifndef VRT_DEFER_GRID_DIV
-#define VRT_DEFER_GRID_DIV 8
-#endif
-// certified-pass waves per exact-pass workgroup (the exact pass's grid; a workgroup loops over the
-// batches beyond it): 8 covers textured frames' deferred pixels in one batch per workgroup (textured
-// C3 0.0843 -> 0.0713 ms against 32; 4 no better; profiles/r03_s11, r03_s12)
-constexpr uint32_t kDeferGridDiv = VRT_DEFER_GRID_DIV;
-#if defined(VRT_DEFER_GRID_DIV_COLOR) && !defined(VRT_DIAGNOSTIC_BUILD)
-#error "VRT_DEFER_GRID_DIV_COLOR is an A/B knob of make variant builds"
-#endif
-#ifndef VRT_DEFER_GRID_DIV_COLOR
-#define VRT_DEFER_GRID_DIV_COLOR VRT_DEFER_GRID_DIV
-#endif
-constexpr uint32_t kDeferGridDivColor = VRT_DEFER_GRID_DIV_COLOR;  // the same for colour-only frames
 
 // ---- launches (vrt_render.hip); all asynchronous on `s` ------------------------------------
 

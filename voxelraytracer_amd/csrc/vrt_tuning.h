@@ -1,0 +1,125 @@
+// vrt_tuning.h — every numeric A/B knob of the kernels and the context: its default, the
+// measurement behind the default, and the constant the code names. Includes <cstdint> only (it
+// preprocesses with a plain host compiler, tests/test_tuning_guard.py).
+#ifndef VRT_TUNING_H
+#define VRT_TUNING_H
+
+#include <cstdint>
+
+// The product library is built with the defaults below. Another value is an A/B build:
+// make variant NAME=w6 DEFS=-DVRT_MIN_WAVES=6 (which defines VRT_DIAGNOSTIC_BUILD).
+#if (defined(VRT_MIN_WAVES) || defined(VRT_DEFER_WAVES) || defined(VRT_EXACT_WAVES) || defined(VRT_TREE_WAVES) || \
+     defined(VRT_FAT_WAVES) || defined(VRT_SPARSE_BATCH) || defined(VRT_SPARSE_BATCH_TEX) ||                    \
+     defined(VRT_SPARSE_BATCH_FAT) || defined(VRT_EXACT_PRIO) || defined(VRT_FWD_CAP) || defined(VRT_WG_WAVES) || \
+     defined(VRT_ORD_DIV) || defined(VRT_ORD_MIN_ROUNDS) || defined(VRT_DEFER_GRID_DIV) ||                      \
+     defined(VRT_DEFER_GRID_DIV_COLOR)) &&                                                                      \
+    !defined(VRT_DIAGNOSTIC_BUILD)
+#error "the VRT_* tuning values are A/B knobs of make variant builds (make variant NAME=... DEFS=-DVRT_...=...)"
+#endif
+
+#ifndef VRT_WG_WAVES
+#define VRT_WG_WAVES 2
+#endif
+#ifndef VRT_MIN_WAVES  // occupancy A/B builds (make variant); images identical at any value
+#define VRT_MIN_WAVES 7
+#endif
+#ifndef VRT_DEFER_WAVES
+#define VRT_DEFER_WAVES 7
+#endif
+#ifndef VRT_EXACT_WAVES
+#define VRT_EXACT_WAVES VRT_MIN_WAVES
+#endif
+#ifndef VRT_TREE_WAVES
+#define VRT_TREE_WAVES 5
+#endif
+#ifndef VRT_FAT_WAVES
+#define VRT_FAT_WAVES 3
+#endif
+#ifndef VRT_SPARSE_BATCH
+#define VRT_SPARSE_BATCH 32
+#endif
+#ifndef VRT_SPARSE_BATCH_TEX
+#define VRT_SPARSE_BATCH_TEX 64
+#endif
+#ifndef VRT_SPARSE_BATCH_FAT
+#define VRT_SPARSE_BATCH_FAT 16
+#endif
+#ifndef VRT_EXACT_PRIO
+#define VRT_EXACT_PRIO 2
+#endif
+#ifndef VRT_FWD_CAP
+#define VRT_FWD_CAP 128
+#endif
+#ifndef VRT_ORD_DIV
+#define VRT_ORD_DIV 4
+#endif
+#ifndef VRT_ORD_MIN_ROUNDS
+#define VRT_ORD_MIN_ROUNDS 1
+#endif
+#ifndef VRT_DEFER_GRID_DIV
+#define VRT_DEFER_GRID_DIV 8
+#endif
+#ifndef VRT_DEFER_GRID_DIV_COLOR
+#define VRT_DEFER_GRID_DIV_COLOR VRT_DEFER_GRID_DIV
+#endif
+
+namespace vrt {
+
+// Waves per workgroup, each rendering an 8x8 pixel tile. Two (a 16x8 tile): a finished
+// workgroup frees its slots two waves at a time, so the dispatcher refills them sooner than with
+// four-wave 16x16 workgroups (C3 -4.4 %, C2 -2.8 %, C4 -8.1 % per frame; one wave per workgroup:
+// C3 -1.7 %, profiles/r02_s06). Images are identical at 1, 2 and 4.
+constexpr int kWgWaves = VRT_WG_WAVES;
+static_assert(kWgWaves == 1 || kWgWaves == 2 || kWgWaves == 4, "1, 2 or 4 waves per workgroup");
+
+// Waves per SIMD the register budget is sized for: 7 -> 72 VGPRs. With certified walks inside the
+// bounce stacks, 64 VGPRs (8 waves) spill in the glass waves that bound a frame: 7 is 2-4 % faster
+// on C1-C4 (profiles/r01_v56_ab_occupancy.log), 6 (80 VGPRs) no better.
+constexpr int kMinWaves = VRT_MIN_WAVES;
+// The certified pass without the exact path (render_kernel's DEFER instances) fits 64 VGPRs (8
+// waves per SIMD) with 8 bytes of scratch, but runs faster at 7 (72 VGPRs, no spills): C3 0.0464 ->
+// 0.0447, C4 0.1751 -> 0.1605, textured C3 -4 % (profiles/r03_s11, r03_s12); 6 is slower again.
+constexpr int kDeferWaves = VRT_DEFER_WAVES;
+// resident waves per SIMD of the exact pass's whole-frame instance (see exact_pass_kernel, WAVES)
+constexpr int kExactWaves = VRT_EXACT_WAVES;
+// resident waves per SIMD of the certified pass with certified trees
+constexpr int kTreeWaves = VRT_TREE_WAVES;
+// resident waves per SIMD of the exact pass's short-band instance (see exact_pass_kernel, WAVES)
+constexpr int kFatWaves = VRT_FAT_WAVES;
+
+// pixels per sparse batch of the exact pass (<= 64): a sparse wave lasts as long as its slowest
+// walk and its steps execute the union of its lanes' sampled steps, so smaller batches shorten the
+// exact pass's span, which the frame's latency and a short run's drain wait for, at more waves: 32
+// with the column-block segments: the driver's 20-frame C3 command 0.0500 -> 0.0464 ms, latency
+// 0.123 -> 0.106 ms, 500 frames +0.8 % (C4 +-0, C2 +1 %); 16: 0.0485 / 0.103 / +2.6 %; 8: 0.0479 /
+// 0.102 / +6 % (profiles/r05_s10)
+constexpr uint32_t kSparseBatch = VRT_SPARSE_BATCH;
+// the same for textured frames: 64 (many more sparse pixels, texel-edge hits: at 32 the extra waves
+// cost textured C3 0.0572 -> 0.0661 ms, C4 0.2329 -> 0.2894; profiles/r05_s30)
+constexpr uint32_t kSparseBatchTex = VRT_SPARSE_BATCH_TEX;
+// the same in the exact pass's short-band instance (see exact_pass_kernel, SB)
+constexpr uint32_t kSparseBatchFat = VRT_SPARSE_BATCH_FAT;
+// wave priority of the whole exact pass (0: only its bounce stacks raise it): its few long waves
+// share SIMDs with the next frames' certified waves; at 2 their chains issue first (C3 0.0395 ->
+// 0.0387 ms per frame, C4 -1 %, the driver's 20-frame run 0.0531 -> 0.0509; 3: C3 0.0389,
+// profiles/r04_exact/)
+constexpr int kExactPrio = VRT_EXACT_PRIO;
+
+// cap of the octant forward distance F (G = F - 1 in 8 bits): 128 vs 64 C4 -1.4 %, C1-C3 +-0.3 % (r03_s42)
+constexpr uint32_t kFwdCap = VRT_FWD_CAP;
+static_assert(kFwdCap >= 3 && kFwdCap <= 255, "F and G are stored in 8 bits");
+
+// first-pass slots per class of a tile-order launch: tiles / (8 kOrdDiv), i.e. up to a quarter of
+// the tiles in the heavy-first pass (C3: ~1600 of a part launch's 8160 tiles are heavy); ord_q_for
+constexpr uint32_t kOrdDiv = VRT_ORD_DIV;
+// dispatch rounds of waves from which an in-lane launch takes the tile order
+constexpr uint32_t kOrdMinRounds = VRT_ORD_MIN_ROUNDS;
+// certified-pass waves per exact-pass workgroup (the exact pass's grid; a workgroup loops over the
+// batches beyond it): 8 covers textured frames' deferred pixels in one batch per workgroup (textured
+// C3 0.0843 -> 0.0713 ms against 32; 4 no better; profiles/r03_s11, r03_s12)
+constexpr uint32_t kDeferGridDiv = VRT_DEFER_GRID_DIV;
+constexpr uint32_t kDeferGridDivColor = VRT_DEFER_GRID_DIV_COLOR;  // the same for colour-only frames
+
+}  // namespace vrt
+
+#endif  // VRT_TUNING_H
