@@ -61,6 +61,23 @@ __device__ __forceinline__ uint32_t path_texel(const Ctx& c, int i, int j, int k
   if (uint32_t(i) >= n || uint32_t(j) >= n || uint32_t(k) >= n) return 0u;
   return cell_texel(c, i, j, k, obase);
 }
+// texel of the cell a crossing of the certified path enters from an in-volume cell: only the
+// crossed axis' index can be outside [0, N), at -1 or N, so one unsigned maximum is that axis'
+// test. No branch around the load: an outside cell reads texel 0 of the ray's octant volume (a -1
+// index has no address in the padded layout), so every address formed lies inside the volume, and
+// the result is replaced by kTexOutside: byte 0 (empty) as path_texel's, plus a bit above the
+// texel's 16 that the walk's MISS test reads (cross_outside) instead of selecting the crossed
+// axis' index again. Kept opaque: one VGPR compare there, no lane mask live across the crossing.
+constexpr uint32_t kTexOutside = 0x10000u;
+__device__ __forceinline__ uint32_t cross_texel(const Ctx& c, int i, int j, int k, uint32_t obase) {
+  const bool outside = max(max(uint32_t(i), uint32_t(j)), uint32_t(k)) >= uint32_t(c.n);
+  const uint32_t idx = mad24(mad24(uint32_t(k), c.p, uint32_t(j)), c.p, uint32_t(i));
+  uint32_t t = load_u16_at(c.vox, outside ? 0u : idx, obase);
+  t = outside ? kTexOutside : t;
+  asm volatile("" : "+v"(t));
+  return t;
+}
+__device__ __forceinline__ bool cross_outside(uint32_t tex) { return tex >= kTexOutside; }
 // byte of a cell the exact walk might sample at a near-edge crossing (plane N: GL_REPEAT copy)
 __device__ __forceinline__ uint32_t alt_byte(const Ctx& c, int i, int j, int k, uint32_t obase) {
   const uint32_t n = uint32_t(c.n);
@@ -82,7 +99,12 @@ __device__ __forceinline__ bool cert_event(uint32_t b, uint32_t medium) {
 // uncertainty from it; len0b: bound of len0. No crossing lies behind the start, so the start
 // cell's box need not cover a cell behind it: it is read from the diagonal neighbour's texel,
 // G(v + s) = F(v) - 1, i.e. the box [v, v + G s].
-template <bool SHADOW>
+// LEAN: the certified pass's walks (render_kernel's DEFER instances, which run without scratch):
+// the same walk with the landing texel loaded unguarded, the crossing's texel without a branch and
+// the planes after a jump from the floored floats; every value it computes is the guarded form's,
+// bit for bit. The other instances keep the guarded forms: they sit at their register limit, and
+// the lean forms moved their scratch use up.
+template <bool SHADOW, bool LEAN = false>
 __device__ __forceinline__ CertResult cert_walk(const Ctx& c, const f3 P, const f3 D, const f3 rcp, const float U,
                                 int cx, int cy, int cz, const float e0, const f3 ed,
                                 const float len0b, const uint32_t medium, const uint32_t tex0 = ~0u) {
@@ -153,13 +175,33 @@ __device__ __forceinline__ CertResult cert_walk(const Ctx& c, const f3 P, const 
       CTRACE(c, 102, G, s1, uj, gam.x, gam.y, gam.z, 0);
       if (uj > s1) {
         // the cell the exact walk is in there: floor(x) moving up, ceil(x) - 1 moving down
-        const float x = Ps.x + uj * Da.x, y = Ps.y + uj * Da.y, z = Ps.z + uj * Da.z;
-        cx = int(__builtin_floorf(x)) ^ mx;
-        cy = int(__builtin_floorf(y)) ^ my;
-        cz = int(__builtin_floorf(z)) ^ mz;
-        sig = mk((float(cx + ux) - P.x) * rcp.x, (float(cy + uy) - P.y) * rcp.y,
-                 (float(cz + uz) - P.z) * rcp.z);
-        tex = path_texel(c, cx, cy, cz, obase);
+        const float fx = __builtin_floorf(Ps.x + uj * Da.x), fy = __builtin_floorf(Ps.y + uj * Da.y),
+                    fz = __builtin_floorf(Ps.z + uj * Da.z);
+        cx = int(fx) ^ mx;
+        cy = int(fy) ^ my;
+        cz = int(fz) ^ mz;
+        // the next planes from the floored floats, sign-folded: (fl_b + 1) - Ps_b is s_b (float(c_b +
+        // u_b) - P_b) exactly (moving down, c_b = ~fl_b and float(c_b) = -(fl_b + 1); negation is
+        // exact, so both forms round the same magnitude) and |1/d_b| = s_b / d_b: the product is
+        // (float(c_b + u_b) - P_b) * rcp_b bit for bit, a zero's sign aside: were fl_b + 1 == Ps_b, a
+        // down-moving axis would get -0 there and +0 here. Every caller starts the walk with no
+        // plane behind the start (sig_b >= 0, see above), and then uj > s1 >= 0 puts the landing at
+        // or ahead of P_b and fl_b + 1 > Ps_b; s1 itself is not clamped, so this is the callers'
+        // precondition, not the loop's. A zero's sign would not matter either: sig enters minima,
+        // compares, differences and fma addends with non-zero products only, where -0 and +0 agree.
+        if constexpr (LEAN)
+          sig = mk(((fx + 1.0f) - Ps.x) * ar.x, ((fy + 1.0f) - Ps.y) * ar.y, ((fz + 1.0f) - Ps.z) * ar.z);
+        else
+          sig = mk((float(cx + ux) - P.x) * rcp.x, (float(cy + uy) - P.y) * rcp.y, (float(cz + uz) - P.z) * rcp.z);
+        // The landing cell is inside the jump box, and the box inside the volume, so its texel is
+        // loaded without path_texel's bounds test: on every axis the sign-folded landing coordinate
+        // is at most that of the plane of sig_b plus G - 1 - kCertMargin cells (uj <= l_b - gam_b,
+        // gam_b >= 0), the box's far face pulled in by 1/64 cell, against a float error of the
+        // coordinate below 2^-16 cell (|x| <= N + 2 <= 2^10 + 2, two roundings); and it is at or
+        // ahead of P_b (uj > s1 >= 0, the callers' precondition above), which the box [v - s, v + (G - 1) s] (at the start: [v, v +
+        // G s] from the cell of P itself) covers. Every cell of the box is in [0, N)^3 (skip_walk's
+        // B(v), vrt_walk.h).
+        tex = LEAN ? cell_texel(c, cx, cy, cz, obase) : path_texel(c, cx, cy, cz, obase);
         continue;
       }
     }
@@ -178,7 +220,7 @@ __device__ __forceinline__ CertResult cert_walk(const Ctx& c, const f3 P, const 
       return r;
     }
     const int nx = cx + (a == 0 ? sx : 0), ny = cy + (a == 1 ? sy : 0), nz = cz + (a == 2 ? sz : 0);
-    const uint32_t ntex = path_texel(c, nx, ny, nz, obase);
+    const uint32_t ntex = LEAN ? cross_texel(c, nx, ny, nz, obase) : path_texel(c, nx, ny, nz, obase);
     const float ga = a == 0 ? gam.x : (a == 1 ? gam.y : gam.z);
     // near-edge flags per other axis: ahead (crossed within the bound after s1) / behind (before).
     // A plane behind counts down to -gam_b, not 0: a ray that starts ON a plane (a shadow or
@@ -240,29 +282,41 @@ __device__ __forceinline__ CertResult cert_walk(const Ctx& c, const f3 P, const 
       const bool ahx = nf & 1u, ahy = nf & 2u, ahz = nf & 4u, bhx = nf & 8u, bhy = nf & 16u,
                  bhz = nf & 32u;
       const int nah = int(ahx) + int(ahy) + int(ahz);
+      // LEAN: each rare block below decodes a flag where it uses it, from a fresh opaque copy of nf,
+      // instead of the six lane masks above (both polarities) being kept across the blocks' loads:
+      // they were the walk's SGPR spills, 24 of the hot instance's 61
+      auto flag = [&](int bit, bool decoded) {
+        if constexpr (LEAN) {
+          uint32_t f = nf;
+          asm volatile("" : "+v"(f));
+          return ((f >> bit) & 1u) != 0u;
+        } else {
+          return decoded;
+        }
+      };
       if (__builtin_popcount(nf) >= 2) {  // near a corner: the 2x2x2 block ahead and the cells behind nc
         for (int q = 1; q < 8; ++q)
           if (cert_event<SHADOW>(alt_byte(c, cx + ((q & 1) ? sx : 0), cy + ((q & 2) ? sy : 0),
                                           cz + ((q & 4) ? sz : 0), obase), medium))
             return r;
-        if ((bhx && cert_event<SHADOW>(alt_byte(c, nx - sx, ny, nz, obase), medium)) ||
-            (bhy && cert_event<SHADOW>(alt_byte(c, nx, ny - sy, nz, obase), medium)) ||
-            (bhz && cert_event<SHADOW>(alt_byte(c, nx, ny, nz - sz, obase), medium)))
+        if ((flag(3, bhx) && cert_event<SHADOW>(alt_byte(c, nx - sx, ny, nz, obase), medium)) ||
+            (flag(4, bhy) && cert_event<SHADOW>(alt_byte(c, nx, ny - sy, nz, obase), medium)) ||
+            (flag(5, bhz) && cert_event<SHADOW>(alt_byte(c, nx, ny, nz - sz, obase), medium)))
           return r;
       } else if (nah) {  // b may be crossed first, or tie: cell + e_b, nc + e_b
-        const int bx = ahx ? sx : 0, by = ahy ? sy : 0, bz = ahz ? sz : 0;
+        const int bx = flag(0, ahx) ? sx : 0, by = flag(1, ahy) ? sy : 0, bz = flag(2, ahz) ? sz : 0;
         if (cert_event<SHADOW>(alt_byte(c, cx + bx, cy + by, cz + bz, obase), medium) ||
             cert_event<SHADOW>(alt_byte(c, nx + bx, ny + by, nz + bz, obase), medium))
           return r;
       } else {  // a may have been crossed before b: nc - e_b
-        if (cert_event<SHADOW>(alt_byte(c, nx - (bhx ? sx : 0), ny - (bhy ? sy : 0),
-                                        nz - (bhz ? sz : 0), obase), medium))
+        if (cert_event<SHADOW>(alt_byte(c, nx - (flag(3, bhx) ? sx : 0), ny - (flag(4, bhy) ? sy : 0),
+                                        nz - (flag(5, bhz) ? sz : 0), obase), medium))
           return r;
       }
     }
     const int na = a == 0 ? nx : (a == 1 ? ny : nz);
     const int sa = a == 0 ? sx : (a == 1 ? sy : sz);
-    if (uint32_t(na) >= uint32_t(c.n)) {  // left the volume (moving away on axis a)
+    if (LEAN ? cross_outside(ntex) : uint32_t(na) >= uint32_t(c.n)) {  // left the volume (moving away on axis a)
       r.res = CERT_MISS;
       return r;
     }
@@ -270,10 +324,21 @@ __device__ __forceinline__ CertResult cert_walk(const Ctx& c, const f3 P, const 
     cy = ny;
     cz = nz;
     tex = ntex;
-    const float np = float(na + (sa > 0 ? 1 : 0));
-    if (a == 0) sig.x = (np - P.x) * rcp.x;
-    else if (a == 1) sig.y = (np - P.y) * rcp.y;
-    else sig.z = (np - P.z) * rcp.z;
+    if constexpr (LEAN) {
+      // the crossed axis' next plane, sign-folded as after a jump: s_a float(na + u_a) is float((na ^
+      // m_a) + 1) (moving down ~na + 1 = -na), so (that - Ps_a) |1/d_a| is (np - P_a) rcp_a bit for
+      // bit (not a zero either: it is s1 + |1/d_a| up to rounding). P and rcp are then dead in the loop.
+      const int ma = a == 0 ? mx : (a == 1 ? my : mz);
+      const float fp = float((na ^ ma) + 1);
+      if (a == 0) sig.x = (fp - Ps.x) * ar.x;
+      else if (a == 1) sig.y = (fp - Ps.y) * ar.y;
+      else sig.z = (fp - Ps.z) * ar.z;
+    } else {
+      const float np = float(na + (sa > 0 ? 1 : 0));
+      if (a == 0) sig.x = (np - P.x) * rcp.x;
+      else if (a == 1) sig.y = (np - P.y) * rcp.y;
+      else sig.z = (np - P.z) * rcp.z;
+    }
   }
   return r;
 }
@@ -330,7 +395,7 @@ __device__ __forceinline__ Hit cert_hit_record(const Ray& ray, const CertResult&
 // TraceWithShadow's colour update (voxel.glsl:395-418) for a certified hit of `ray`: the shadow
 // bit by a certified shadow walk from the hit, unless it cannot change the brightness (lit ==
 // ambient). false: unsure (colour untouched).
-template <bool TEX = false>
+template <bool TEX = false, bool LEAN = false>
 __device__ __forceinline__ bool cert_shade_hit(const Ctx& c, const Ray& ray, const CertResult& h,
                                                const Hit& hh, f3& color, float4 col = float4()) {
   const float lit = lit_brightness<TEX>(hh, c.sun_n, ray.dir);
@@ -355,7 +420,7 @@ __device__ __forceinline__ bool cert_shade_hit(const Ctx& c, const Ray& ray, con
     const uint32_t n = uint32_t(c.n);
     if (uint32_t(ax) >= n || uint32_t(ay) >= n || uint32_t(az) >= n) { CERT_DIAG(7); return false; }
     if (cert_event<true>(cell_texel(c, ax, ay, az, sob) & kVoxMask, 0u)) { CERT_DIAG(7); return false; }
-    const CertResult s = cert_walk<true>(c, hh.point, S, c.sun_rcp, c.max_len - hh.len, ax, ay, az,
+    const CertResult s = cert_walk<true, LEAN>(c, hh.point, S, c.sun_rcp, c.max_len - hh.len, ax, ay, az,
                                          h.eu, ed, hh.len, 0u, t0);
     if (s.res == CERT_UNSURE) { CERT_DIAG(8); return false; }
     CERT_DIAG(9);
@@ -374,6 +439,7 @@ __device__ __forceinline__ bool cert_shade_hit(const Ctx& c, const Ray& ray, con
 // march(): leaving a glass medium refracts it in place (:357-380), and the walk restarts from
 // that crossing. (cx, cy, cz), e0, ed: the start (cert_start). Returns the first non-air event
 // (CERT_HIT), CERT_MISS or CERT_UNSURE.
+template <bool LEAN = false>
 __device__ __forceinline__ CertResult cert_march(const Ctx& c, Ray& ray, int cx, int cy, int cz, float e0, f3 ed) {
   CertResult h;
   h.res = CERT_UNSURE;
@@ -383,8 +449,8 @@ __device__ __forceinline__ CertResult cert_march(const Ctx& c, Ray& ray, int cx,
     if (!fast_path_ok(ray.dir) || !(e0 < kCertMaxOrigin)) { CERT_DIAG(24); return h; }
     const f3 rcp = mk(__builtin_amdgcn_rcpf(ray.dir.x), __builtin_amdgcn_rcpf(ray.dir.y),
                       __builtin_amdgcn_rcpf(ray.dir.z));
-    h = cert_walk<false>(c, ray.pos, ray.dir, rcp, c.max_len - ray.len, cx, cy, cz, e0, ed, ray.len,
-                         medium);
+    h = cert_walk<false, LEAN>(c, ray.pos, ray.dir, rcp, c.max_len - ray.len, cx, cy, cz, e0, ed, ray.len,
+                               medium);
     if (h.res == CERT_UNSURE) CERT_DIAG(25);
     if (h.res != CERT_HIT || h.byte != 0u) return h;
     CERT_DIAG(30);
@@ -564,7 +630,7 @@ __device__ __forceinline__ bool tree_refraction(const Ctx& c, const Ray& ray, co
 // walk of the ray the reference pops next (ray, h updated). kTreeDone: the tree is complete (colour
 // final); kTreeUnsure: it cannot be certified (colour meaningless); kTreeNext: continue with ray, h.
 constexpr int kTreeNext = 0, kTreeDone = 1, kTreeUnsure = -1;
-template <int NL>
+template <int NL, bool LEAN = false>
 __device__ __forceinline__ int tree_step(const Ctx& c, int max_refl, int max_transp, Ray& ray, CertResult& h,
                                          f3& color, bool& pending, float4* __restrict__ lta,
                                          float* __restrict__ ltb) {
@@ -583,7 +649,7 @@ __device__ __forceinline__ int tree_step(const Ctx& c, int max_refl, int max_tra
     apply_sky_color(c, ray, color);
   } else {
     const Hit hh = cert_hit_record(ray, h);
-    if (!cert_shade_hit<false>(lc, ray, h, hh, color)) { CERT_DIAG(22); return kTreeUnsure; }
+    if (!cert_shade_hit<false, LEAN>(lc, ray, h, hh, color)) { CERT_DIAG(22); return kTreeUnsure; }
     // children (:440-448): the reflection ray is pushed first, the refraction ray second and
     // popped first; the stack (R + T + 1 entries) never fills with at most one ray waiting
     const uint32_t m = mat_id(h.byte);
@@ -611,7 +677,7 @@ __device__ __forceinline__ int tree_step(const Ctx& c, int max_refl, int max_tra
     t = tree_get<NL>(lta, ltb);
   }
   ray = t.ray;
-  h = cert_march(c, ray, t.cx, t.cy, t.cz, t.e0, t.ed);
+  h = cert_march<LEAN>(c, ray, t.cx, t.cy, t.cz, t.e0, t.ed);
   if (h.res == CERT_UNSURE) { CERT_DIAG(21); return kTreeUnsure; }
   CERT_DIAG(23);
   return kTreeNext;
@@ -625,7 +691,7 @@ __device__ __forceinline__ int tree_step(const Ctx& c, int max_refl, int max_tra
 // (Walking the primary ray through this loop too, one walk call site for every ray, made the
 // certified pass 3x slower: every pixel then carried the tree's registers; r06_s4.)
 // lta / ltb: this lane's LDS slot (tree_put; NL lanes per workgroup).
-template <int NL>
+template <int NL, bool LEAN = false>
 __device__ __forceinline__ bool cert_tree(const Ctx& c, int max_refl, int max_transp, const Ray& ray0,
                                           const CertResult& h0, f3& color_out, float4* __restrict__ lta,
                                           float* __restrict__ ltb) {
@@ -635,7 +701,7 @@ __device__ __forceinline__ bool cert_tree(const Ctx& c, int max_refl, int max_tr
   bool pending = false;  // a reflection ray waits in the LDS slot
   CERT_DIAG(16);
   for (;;) {
-    const int r = tree_step<NL>(c, max_refl, max_transp, ray, h, color, pending, lta, ltb);
+    const int r = tree_step<NL, LEAN>(c, max_refl, max_transp, ray, h, color, pending, lta, ltb);
     if (r == kTreeUnsure) return false;
     if (r == kTreeDone) break;
   }
@@ -938,7 +1004,7 @@ __device__ __forceinline__ bool cert_texel(const Ctx& c, const Ray& ray, const C
 // TREE (colour-only): a glass primary hit's bounce tree by certified walks too (cert_tree; ltb and c.ax its
 // LDS slot), instead of leaving the whole pixel to the exact path.
 // us_out: the primary walk's certified prefix (CertResult::us) for the exact path, -1 if none.
-template <bool TEX = false, bool TREE = false, int NL = kWgThreads>
+template <bool TEX = false, bool TREE = false, int NL = kWgThreads, bool LEAN = false>
 __device__ __forceinline__ bool cert_pixel(const Ctx& c, const Ray& ray0, f3& color_out, int max_refl = 0,
                                            int max_transp = 0, float* __restrict__ ltb = nullptr,
                                            float* us_out = nullptr) {
@@ -951,8 +1017,8 @@ __device__ __forceinline__ bool cert_pixel(const Ctx& c, const Ray& ray0, f3& co
   }
   // hardware reciprocals (<= 1 ulp): the certified walk only needs its own error bounded
   const f3 rcp = mk(__builtin_amdgcn_rcpf(D.x), __builtin_amdgcn_rcpf(D.y), __builtin_amdgcn_rcpf(D.z));
-  CertResult h = cert_walk<false>(c, P, D, rcp, c.max_len - ray0.len, cx, cy, cz, 0.0f,
-                                  mk(0.0f, 0.0f, 0.0f), 0.0f, 0u);
+  CertResult h = cert_walk<false, LEAN>(c, P, D, rcp, c.max_len - ray0.len, cx, cy, cz, 0.0f,
+                                        mk(0.0f, 0.0f, 0.0f), 0.0f, 0u);
   if (us_out) *us_out = h.us;
   CERT_DIAG_ONLY(cert_diag_iters(10, h.iters);)
   if (h.res == CERT_UNSURE) { CERT_DIAG(1); return false; }
@@ -965,13 +1031,13 @@ __device__ __forceinline__ bool cert_pixel(const Ctx& c, const Ray& ray0, f3& co
   }
   if (mat_id(h.byte) == 2u) {  // only glass spawns secondary rays (:440-448)
     CERT_DIAG(3);
-    if constexpr (TREE && !TEX) return cert_tree<NL>(c, max_refl, max_transp, ray0, h, color_out, c.ax, ltb);
+    if constexpr (TREE && !TEX) return cert_tree<NL, LEAN>(c, max_refl, max_transp, ray0, h, color_out, c.ax, ltb);
     return false;
   }
   const Hit hh = cert_hit_record(ray0, h);
   float4 col = float4();
   if (TEX && !cert_texel(c, ray0, h, hh, col)) return false;
-  if (!cert_shade_hit<TEX>(c, ray0, h, hh, color, col)) return false;
+  if (!cert_shade_hit<TEX, LEAN>(c, ray0, h, hh, color, col)) return false;
   color_out = color;
   return true;
 }

@@ -430,6 +430,7 @@ vrt::KArgs make_args(const vrt_ctx* ctx, const Shard& s, const vrt_camera* cam, 
   a.atlas_tex_size = p->atlas_texture_size;
   a.atlas = s.d_atlas;
   a.alpha = 1.0f;
+  a.vdiv_ok = 0;  // set per launch (launch)
   a.prev = nullptr;
   a.cur = nullptr;
   a.raw = nullptr;
@@ -614,6 +615,28 @@ OrderSlot* launch_state_begin(const vrt_ctx* ctx, Shard& s, vrt::KArgs& a, hipSt
   return slot;
 }
 
+// The vertex stage's divisions (primary_ray: n4.xyz / n4.w and f4.xyz / f4.w, with n4, f4 =
+// inv_pv^T (ndx, ndy, -+1, 1)) take Markstein's sequence when every operand's magnitude is in
+// [2^-60, 2^60]. All but the numerators' lower bound follows from the matrix, since |ndx|, |ndy| <=
+// 1 (a correctly rounded quotient in [0, 2], minus 1): component i is at most S_i = |m_0i| + |m_1i|
+// + |m_2i| + |m_3i| in magnitude, and the denominators are at least |m_33 -+ m_23| - |m_03| -
+// |m_13|. The kernel forms them in float, four products and three sums: within 2^-21 S_i of the
+// real value, allowed for here as 2^-20 S_i, and the bounds are held to 2^59 and 2^-59, one binade
+// inside the kernel's. true: every pixel's operands pass all of the kernel's tests except
+// "|numerator| >= 2^-60" (NaN or infinite entries: false).
+bool vertex_div_ranges_ok(const float* m) {
+  const double hi = 0x1p59, lo = 0x1p-59;
+  double sum[4];
+  for (int i = 0; i < 4; ++i) {
+    sum[i] = std::fabs(double(m[i])) + std::fabs(double(m[4 + i])) + std::fabs(double(m[8 + i])) +
+             std::fabs(double(m[12 + i]));
+    if (!(sum[i] * (1.0 + 0x1p-20) <= hi)) return false;
+  }
+  const double side = std::fabs(double(m[3])) + std::fabs(double(m[7])) + sum[3] * 0x1p-20;
+  return std::fabs(double(m[15]) - double(m[11])) - side >= lo &&  // n4.w
+         std::fabs(double(m[15]) + double(m[11])) - side >= lo;    // f4.w
+}
+
 // One band launch on `st` (heavy-first tile order for uncounted launches), then, when counting,
 // the fold of the counter replicas into `cnt` (accumulating). ev_begin / ev_end: optional device
 // timestamps of the kernel's start and end.
@@ -621,6 +644,9 @@ void launch(const vrt_ctx* ctx, Shard& s, vrt::KArgs a, float4* out, vrt_hit* hi
             hipStream_t st, hipEvent_t ev_begin = nullptr, hipEvent_t ev_end = nullptr, bool allow_defer = true,
             bool lone = false) {
   const bool stats = hit || cnt;
+  a.vdiv_ok = vertex_div_ranges_ok(a.inv_pv) ? 1u : 0u;
+  for (int f = 1; f < a.nframes; ++f)
+    if (!vertex_div_ranges_ok(a.fb[f - 1].inv_pv)) a.vdiv_ok = 0u;
   OrderSlot* slot = stats ? nullptr : launch_state_begin(ctx, s, a, st, allow_defer || lone, lone);
   vrt::launch_render(a, stats, s.d_vox_pad, out, hit, cnt ? s.d_cnt_rep : nullptr, st, ev_begin, ev_end);
   slot_launched(s, slot, st);
@@ -644,6 +670,8 @@ int volume_alloc(vrt_ctx* ctx, Shard& s, int32_t n) {
     s.d_vox_pad = nullptr;
   }
   if (!s.d_vox) {
+    // (no guard band around the packed volumes: the certified pass's unguarded loads, cert_walk's
+    // LEAN forms, only form addresses of cells in [0, N)^3, or texel 0 for a crossing that leaves)
     const size_t bytes = size_t(n) * n * n, pbytes = size_t(n + 1) * (n + 1) * (n + 1) * 2 * size_t(octants);
     if (hipMalloc(&s.d_vox, bytes) != hipSuccess ||
         hipMalloc(&s.d_tmp, (octants == 8 ? 3 : 2) * bytes) != hipSuccess ||

@@ -86,7 +86,7 @@ __device__ __forceinline__ uint32_t xcc_id() {
 }
 
 #define STAMP_WAVE_BEGIN(wave)                                 \
-  const uint32_t wave_lin = blockIdx.x * kWgWaves + (wave);    \
+  const uint32_t wave_lin = ((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * kWgWaves + (wave); \
   const unsigned long long t_start = __builtin_amdgcn_s_memrealtime()
 #define STAMP_WAVE_CERT(need_exact)                                                       \
   do {                                                                                    \

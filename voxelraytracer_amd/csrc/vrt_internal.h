@@ -34,6 +34,10 @@ struct KArgs {
   const uint32_t* atlas;
   // temporal epilogue (cur != nullptr): RGB8 store + temporal.glsl blend instead of float RGBA
   float alpha;
+  // the vertex stage's division operands are in range for every pixel and frame of the launch
+  // (vertex_div_ranges_ok, vrt_context.cpp; primary_ray's div3_rn). In the padding before `prev`:
+  // the layout is unchanged.
+  uint32_t vdiv_ok;
   const uint32_t* prev;  // last filtered frame (RGBA8 words), band-local like the output
   uint32_t* cur;         // filtered frame written here
   uint32_t* raw;         // optional: the quantised ray-trace frame (the reference's rayTrace FBO)

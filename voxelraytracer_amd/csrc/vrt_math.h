@@ -122,9 +122,17 @@ __device__ __forceinline__ bool zero_noise_exact(f3 d) {
   return int(__float_as_uint(d.x) != nz) & int(__float_as_uint(d.y) != nz) &
          int(__float_as_uint(d.z) != nz) & int(d.x == d.x) & int(d.y == d.y) & int(d.z == d.z);
 }
+// The same predicate as one class test per component: -0, signalling NaN or quiet NaN (v_cmp_class
+// bits 5, 0, 1). The certified pass's form (LEAN); the truth table is the bit tests' on every pattern.
+__device__ __forceinline__ bool zero_noise_exact_class(f3 d) {
+  constexpr int kNegZeroOrNan = 0x020 | 0x001 | 0x002;
+  return !(__builtin_amdgcn_classf(d.x, kNegZeroOrNan) | __builtin_amdgcn_classf(d.y, kNegZeroOrNan) |
+           __builtin_amdgcn_classf(d.z, kNegZeroOrNan));
+}
+template <bool LEAN = false>
 __device__ __forceinline__ f3 randomize(f3 dir, f3 pos, float randomness, float seed) {
   f3 r = mk(0.0f, 0.0f, 0.0f);
-  if (!(randomness == 0.0f && zero_noise_exact(dir))) {
+  if (!(randomness == 0.0f && (LEAN ? zero_noise_exact_class(dir) : zero_noise_exact(dir)))) {
     const f3 p = mk((pos.x + dir.x) + seed, (pos.y + dir.y) + seed, (pos.z + dir.z) + seed);
     const float dx = random4(p.x, p.y, p.z, 0.0f + seed);
     const float dy = random4(p.x, p.y, p.z, 0.5f + seed);

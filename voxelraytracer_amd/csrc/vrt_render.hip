@@ -193,14 +193,33 @@ __device__ __forceinline__ bool markstein_safe(float x) {
   const float m = __builtin_fabsf(x);
   return m >= 0x1p-60f && m <= 0x1p60f;
 }
-__device__ __forceinline__ f3 div3_rn(float x, float y, float z, float d) {
-  if (markstein_safe(x) && markstein_safe(y) && markstein_safe(z) && markstein_safe(d)) {
+// ranges_ok (KArgs::vdiv_ok, wave-uniform; read by the certified pass's instances only, LEAN): the
+// host has proved |x|, |y|, |z| <= 2^60 and |d| in [2^-60, 2^60] for every pixel of the launch, so
+// only the numerators' lower bound is left to the lane: the smallest |numerator| against 2^-60
+// (the values are finite, so the minimum drops no NaN). Each lane takes the same sequence either way.
+template <bool LEAN = false>
+__device__ __forceinline__ f3 div3_rn(float x, float y, float z, float d, bool ranges_ok = false) {
+  bool safe;
+  if constexpr (LEAN) {
+    // the same test in two parts: what the host may have proved (a wave-uniform branch around it;
+    // it also rejects NaN numerators, which the minimum drops), and the numerators' lower bound
+    bool rest = true;
+    if (!ranges_ok)
+      rest = int(__builtin_fabsf(x) <= 0x1p60f) & int(__builtin_fabsf(y) <= 0x1p60f) &
+             int(__builtin_fabsf(z) <= 0x1p60f) & int(markstein_safe(d));
+    safe = rest & (__builtin_fminf(__builtin_fminf(__builtin_fabsf(x), __builtin_fabsf(y)), __builtin_fabsf(z)) >=
+                   0x1p-60f);
+  } else {
+    safe = markstein_safe(x) && markstein_safe(y) && markstein_safe(z) && markstein_safe(d);
+  }
+  if (safe) {
     const float r = rcp_newton(d);  // |d| in [2^-60, 2^60]: RN(1/d)
     return mk(div_rn(x, d, r), div_rn(y, d, r), div_rn(z, d, r));
   }
   return mk(x / d, y / d, z / d);
 }
 
+template <bool LEAN = false>
 __device__ __forceinline__ Ray primary_ray(const KArgs& a, const float* __restrict__ inv_pv, const Ctx& c, int px,
                                            int py) {
   // (2 (p + 0.5)) / W with RN(1/W) from the host: the numerator is in (0, 2W), W <= 32768
@@ -213,11 +232,12 @@ __device__ __forceinline__ Ray primary_ray(const KArgs& a, const float* __restri
     n4[i] = (base + inv_pv[2 * 4 + i] * -1.0f) + inv_pv[3 * 4 + i] * 1.0f;
     f4[i] = (base + inv_pv[2 * 4 + i] * 1.0f) + inv_pv[3 * 4 + i] * 1.0f;
   }
-  const f3 vnear = div3_rn(n4[0], n4[1], n4[2], n4[3]);
-  const f3 vdir = div3_rn(f4[0], f4[1], f4[2], f4[3]) - vnear;
+  const bool ranges_ok = LEAN && a.vdiv_ok != 0u;
+  const f3 vnear = div3_rn<LEAN>(n4[0], n4[1], n4[2], n4[3], ranges_ok);
+  const f3 vdir = div3_rn<LEAN>(f4[0], f4[1], f4[2], f4[3], ranges_ok) - vnear;
   Ray ray;
   ray.pos = mk(vnear.x + c.fn * 0.5f, vnear.y + c.fn * 0.5f, vnear.z + c.fn * 0.5f);
-  ray.dir = randomize(normalize3(vdir), vnear, a.ray_noise, c.time);
+  ray.dir = randomize<LEAN>(normalize3(vdir), vnear, a.ray_noise, c.time);
   ray.len = 0.0f;
   ray.energy = 1.0f;
   ray.voxel = 0;
@@ -395,16 +415,32 @@ __global__ void __launch_bounds__(kWgThreads, TREE ? kTreeWaves : (DEFER ? kDefe
   // every wave (~1.8 KB/wave of scratch writes, most of the excess WRITE_SIZE over the frame).
   const int wave = __builtin_amdgcn_readfirstlane(int(threadIdx.x) >> 6);
   STAMP_WAVE_BEGIN(wave);
-  uint32_t tile = blockIdx.x;
-  if constexpr (ORD) {  // heavy-first tile order (a.order): its own instance
-    tile = ordered_tile(a, blockIdx.x);
-    if (tile == ~0u) return;  // whole workgroup: its tile is rendered by another slot
+  uint32_t tile = 0u;  // the linear tile: set and used by the 1-D instances only (ORD's epilogue)
+  uint32_t fr = 0u, tx, ty;
+  if constexpr (DEFER) {
+    // the certified pass is launched as a tiles_x x tiles_y (x frames) grid (launch_render): the
+    // tile's column, row and frame are the workgroup id's components, no division. Workgroups are
+    // dispatched x fastest, then y, then z: the same order as the linear grid tile = (fr * tiles_y
+    // + ty) * tiles_x + tx, so workgroup L still lands on XCD L % 8. (The linear tile itself is
+    // not needed here: the deferred list's segment is the tile's column block, whose division by
+    // tiles_x below is the one left, in waves that defer a pixel.)
+    static_assert(!ORD, "the certified pass has no tile order");
+    tx = blockIdx.x;
+    ty = blockIdx.y;
+    if constexpr (FB) fr = blockIdx.z;
+  } else {
+    tile = blockIdx.x;
+    if constexpr (ORD) {  // heavy-first tile order (a.order): its own instance
+      tile = ordered_tile(a, blockIdx.x);
+      if (tile == ~0u) return;  // whole workgroup: its tile is rendered by another slot
+    }
+    tile = __builtin_amdgcn_readfirstlane(tile);
+    // frame batches: the tile's frame and its tile within the frame (wave-uniform)
+    if constexpr (FB) fr = uint32_t(__builtin_amdgcn_readfirstlane(int(tile / a.frame_tiles)));
+    const uint32_t ltile = tile - fr * a.frame_tiles;
+    ty = ltile / a.tiles_x;
+    tx = ltile - ty * a.tiles_x;
   }
-  tile = __builtin_amdgcn_readfirstlane(tile);
-  // frame batches: the tile's frame and its tile within the frame (wave-uniform)
-  const uint32_t fr = FB ? uint32_t(__builtin_amdgcn_readfirstlane(int(tile / a.frame_tiles))) : 0u;
-  const uint32_t ltile = tile - fr * a.frame_tiles;
-  const uint32_t ty = ltile / a.tiles_x, tx = ltile - ty * a.tiles_x;
   const int px = pixel_x(tx, wave, lane_id());
   const int li = pixel_row(ty, wave, lane_id());
   const bool valid = px < a.width && li < a.rows;
@@ -428,7 +464,7 @@ __global__ void __launch_bounds__(kWgThreads, TREE ? kTreeWaves : (DEFER ? kDefe
     constexpr int kPool = std::max(kAxFloats + kStkFloats, 4);
     __shared__ float4 lds_pool[kPool / 4];
     c.ax = &lds_pool[threadIdx.x * kAxLane];
-    const Ray ray = primary_ray(a, FB ? frame_view(a, fr).pv : a.inv_pv, c, px, frame_row(a, li));
+    const Ray ray = primary_ray<DEFER>(a, FB ? frame_view(a, fr).pv : a.inv_pv, c, px, frame_row(a, li));
     k.c[VRT_CNT_PIXELS] = 1;
     k.c[VRT_CNT_PRIMARY_RAYS] = 1;
     uint32_t steps = 0, flags = 0;
@@ -447,7 +483,7 @@ __global__ void __launch_bounds__(kWgThreads, TREE ? kTreeWaves : (DEFER ? kDefe
       tstk = reinterpret_cast<float*>(lds_pool) + kAxFloats + threadIdx.x;   // (and c.ax: tree_put)
     }
     float us = -1.0f;  // the primary walk's certified prefix, for the exact path
-    const bool need_exact = CERT < 2 || !cert_pixel<TEX, TREE>(c, ray, color, a.max_refl, a.max_transp, tstk, &us);
+    const bool need_exact = CERT < 2 || !cert_pixel<TEX, TREE, kWgThreads, DEFER>(c, ray, color, a.max_refl, a.max_transp, tstk, &us);
     STAMP_WAVE_CERT(need_exact);
     if constexpr (DEFER) {
       deferred = need_exact;
@@ -640,7 +676,9 @@ void launch_render(const KArgs& a, bool stats, const uint16_t* vox, float4* out,
   if (a.defer && !stats && a.cert == 2) {
     // certified pass, then the exact pass over the pixels it deferred (no tile order: the
     // certified pass has no long waves)
-    const dim3 g1(a.tiles),
+    // the certified pass's grid: tile columns x tile rows x frames (render_kernel reads its tile
+    // from the workgroup id's components); the same workgroups in the same dispatch order as a.tiles
+    const dim3 g1(a.tiles_x, a.frame_tiles / a.tiles_x, uint32_t(a.nframes)),
         g2(a.exact_grid ? a.exact_grid
                         : std::max(64u, a.tiles * uint32_t(kWgWaves) / (a.textured ? kDeferGridDiv : kDeferGridDivColor)));
     // frame batches (a.nframes > 1): their own instances
