@@ -155,8 +155,41 @@ int vrt_upload_volume_device(vrt_ctx* ctx, const uint8_t* d_voxels, int32_t n, v
  * Every device of the context builds its own replica (no transfer). */
 int vrt_build_scene_device(vrt_ctx* ctx, int32_t scene, int32_t n, uint32_t seed, void* hip_stream);
 
+/* Added within v15 (detect by symbol lookup): in-place voxel edits, the glTexSubImage3D of this
+ * boundary. Replace the voxels of the box [origin, origin+extent) of the resident volume with
+ * `voxels` (host, extent[0]*extent[1]*extent[2] bytes, x fastest inside the box) and bring every
+ * packed skip-distance volume, on every device of the context, to exactly the bytes a full
+ * vrt_upload_volume of the edited volume would produce. Skip distances have bounded support (the
+ * forward distance is capped at 128, the centred one at 64), so only the packed texels of
+ * vrt_volume_edit_plan's boxes are rebuilt, by region passes in the resident scratch: the call
+ * allocates nothing, and the layout, N and the octant count stay. An edit that changes no cell's
+ * emptiness (materials only) rewrites the box's voxel bytes alone. The glass share behind
+ * vrt_set_certified's automatic mode moves by the box's counts, so vrt_certified() equals that of a
+ * fresh upload. Ordering is the upload's: the call waits for the frames in flight on the context's
+ * lanes (they read the packed volume) and returns when the edit is complete on every device.
+ * VRT_ERR_NO_VOLUME without a resident volume; VRT_ERR_INVALID for null pointers, an extent <= 0
+ * or a box not inside [0, N)^3; a failed call leaves the volume as it was. */
+int vrt_update_volume_region(vrt_ctx* ctx, const int32_t origin[3], const int32_t extent[3],
+                             const uint8_t* voxels);
+/* Same from a DEVICE buffer on the context's first device, ordered on `hip_stream`; the other
+ * devices receive the box by peer copies. */
+int vrt_update_volume_region_device(vrt_ctx* ctx, const int32_t origin[3], const int32_t extent[3],
+                                    const uint8_t* d_voxels, void* hip_stream);
+/* Added within v15. Host arithmetic, no GPU (like vrt_block_band_plan): per packed volume
+ * o < octants (8 or 1; bit a of o: the octant's step on axis a is -1), out[o*6+0..5] =
+ * {x0,y0,z0,x1,y1,z1}, the half-open box of packed texels in [0, N)^3 that an edit of the box
+ * [origin, origin+extent) = [lo, hi) may change. Octants, per axis with step s: the anchors whose
+ * forward distance F can change are [lo-127, hi-1] (s = +1) or [lo, hi-1+127] (s = -1), the texel
+ * G(w) = F(w - s) - 1 shifts them by s, the edit's own cells join for the voxel bytes, and the
+ * result is clipped to [0, N). Single layout: [lo-63, hi-1+63] per axis, clipped. (Texels at
+ * coordinate N, which repeat voxel 0, are rewritten besides when the box holds coordinate 0.)
+ * Returns octants, or VRT_ERR_INVALID (null pointers, octants not 8 or 1, N not a power of two in
+ * [2, 1024], a box not inside the volume). */
+int vrt_volume_edit_plan(int32_t n, int32_t octants, const int32_t origin[3], const int32_t extent[3],
+                         int32_t* out);
+
 /* Device pointer of the resident volume (N^3 bytes, canonical layout), e.g. for a broadcast.
- * NULL if none. */
+ * NULL if none. An edit (vrt_update_volume_region) updates it in place. */
 const uint8_t* vrt_volume_device_ptr(const vrt_ctx* ctx);
 
 /* Diagnostic: copy the kernel's device volume to `out` (count >= octants x (N+1)^3, see

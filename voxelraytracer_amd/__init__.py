@@ -206,6 +206,19 @@ def block_copy_plan(width: int, height: int, k: int, row_block: int, elem_bytes:
     return [tuple(int(v) for v in row) for row in out.reshape(k * 2, 7) if row[6] > 0]
 
 
+def volume_edit_plan(n: int, octants: int, origin, extent):
+    """vrt_volume_edit_plan: per packed volume o < octants (8 or 1), the half-open box (x0, y0, z0,
+    x1, y1, z1) of packed texels in [0, n)^3 that an edit of the box [origin, origin + extent)
+    (x, y, z order) may change. Host arithmetic, no GPU."""
+    o3 = (C.c_int32 * 3)(*(int(v) for v in origin))
+    e3 = (C.c_int32 * 3)(*(int(v) for v in extent))
+    out = np.zeros(max(int(octants), 1) * 6, np.int32)
+    k = lib().vrt_volume_edit_plan(n, octants, C.byref(o3), C.byref(e3), out.ctypes.data)
+    if k < 0:
+        raise VrtError(k, "vrt_volume_edit_plan")
+    return [tuple(int(v) for v in row) for row in out.reshape(-1, 6)[:k]]
+
+
 def comm_unique_id() -> bytes:
     """vrt_comm_unique_id: a new RCCL unique id (rank 0 of a one-process-per-GPU job creates one
     per communicator and the job distributes them)."""
@@ -269,6 +282,28 @@ class Renderer:
         self._check(self._lib.vrt_upload_volume_device(self._h, d_voxels, n, stream or None),
                     "vrt_upload_volume_device")
         self.n = n
+
+    def update_volume(self, origin, block: np.ndarray):
+        """In-place edit (vrt_update_volume_region): `block`, a uint8 array indexed [z][y][x],
+        replaces the voxels of the box at `origin` = (x, y, z); the packed skip-distance volumes
+        become exactly those of a full upload of the edited volume, by a regional rebuild."""
+        b = np.ascontiguousarray(block, dtype=np.uint8)
+        if b.ndim != 3:
+            raise ValueError("block must be indexed [z][y][x]")
+        o3 = (C.c_int32 * 3)(*(int(v) for v in origin))
+        e3 = (C.c_int32 * 3)(b.shape[2], b.shape[1], b.shape[0])
+        self._check(self._lib.vrt_update_volume_region(self._h, C.byref(o3), C.byref(e3), b.ctypes.data),
+                    "vrt_update_volume_region")
+
+    def update_volume_device(self, origin, extent, d_ptr: int, stream: int = 0):
+        """update_volume from a device buffer on the first device (extent[0] * extent[1] * extent[2]
+        bytes, x fastest inside the box; e.g. a torch uint8 tensor's data_ptr()), ordered on
+        `stream`. origin and extent are (x, y, z)."""
+        o3 = (C.c_int32 * 3)(*(int(v) for v in origin))
+        e3 = (C.c_int32 * 3)(*(int(v) for v in extent))
+        self._check(self._lib.vrt_update_volume_region_device(self._h, C.byref(o3), C.byref(e3), d_ptr or None,
+                                                              stream or None),
+                    "vrt_update_volume_region_device")
 
     def debug_packed_volume(self) -> np.ndarray:
         """The kernel's device volumes [octant][z][y][x] ((N+1)^3 u16 voxel | G << 8 each; 8

@@ -96,7 +96,9 @@ HIT_DTYPE = [("voxel_index", "<i4"), ("ray_length", "<f4"), ("steps", "<u4"), ("
 # name -> (restype, argtypes): every function include/vrt.h declares
 # entry points added after ABI v12 (an older build loaded by VRT_LIB with VRT_LIB_ABI=<its version>
 # may lack exactly these)
-ADDED_IN = {"vrt_render_temporal_batch_async": 14, "vrt_set_cert_trees": 15}
+ADDED_IN = {"vrt_render_temporal_batch_async": 14, "vrt_set_cert_trees": 15,
+            # added within v15 (in-place edits): a v15 build from before them lacks these three
+            "vrt_update_volume_region": 16, "vrt_update_volume_region_device": 16, "vrt_volume_edit_plan": 16}
 
 SIGNATURES = {
     "vrt_abi_version": (C.c_int, []),
@@ -123,6 +125,13 @@ SIGNATURES = {
     "vrt_upload_volume": (C.c_int, [C.c_void_p, C.POINTER(Volume)]),
     "vrt_upload_volume_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "vrt_volume_device_ptr": (C.c_void_p, [C.c_void_p]),
+    # added within v15 (no version bump: detect by symbol lookup): in-place voxel edits
+    "vrt_update_volume_region": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32 * 3), C.POINTER(C.c_int32 * 3),
+                                           C.c_void_p]),
+    "vrt_update_volume_region_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32 * 3),
+                                                  C.POINTER(C.c_int32 * 3), C.c_void_p, C.c_void_p]),
+    "vrt_volume_edit_plan": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int32 * 3),
+                                       C.POINTER(C.c_int32 * 3), C.c_void_p]),
     "vrt_build_scene_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p]),
     "vrt_debug_packed_volume": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
     "vrt_debug_collectives": (C.c_int, [C.c_void_p]),

@@ -62,6 +62,7 @@ size_t defer_words(uint32_t tiles, uint32_t tiles_x) {
 // it costs nothing in the steady state (with four slots every frame waited for its lane
 // predecessor's consumption through two command-processor hops: C3 0.0719 vs 0.0596 ms per frame).
 constexpr int kRing = 8;
+constexpr size_t kVstatWords = 8;  // Shard::d_vstats: 2 counts of an upload, 5 of an edit's box
 static_assert(kRing % kLanes == 0, "a ring slot is always written from the same lane");
 
 struct OrderSlot {
@@ -93,7 +94,8 @@ struct Shard {
   int32_t n = 0, octants = 0;
   bool cert_auto = true;   // automatic certified-pixel choice for the resident volume
   bool has_glass = true;   // the resident volume has glass (bounce stacks; tile order)
-  unsigned long long* d_vstats = nullptr;  // glass and non-empty voxel counts
+  unsigned long long* d_vstats = nullptr;  // glass and non-empty voxel counts (kVstatWords words)
+  unsigned long long glass = 0, non_empty = 0;  // of the resident volume (an edit moves them by its box's)
   // counters
   unsigned long long* d_cnt = nullptr;      // VRT_CNT_COUNT totals of a synchronous render
   unsigned long long* d_cnt_rep = nullptr;  // kCntReplicas x VRT_CNT_COUNT, kept zeroed
@@ -697,6 +699,14 @@ int volume_alloc_all(vrt_ctx* ctx, int32_t n) {
   return VRT_OK;
 }
 
+// certified walks cannot settle glass pixels (their secondary rays start at the exact hit point) and
+// a glass pixel pays the certified primary walk before the exact path: the automatic mode turns
+// them off when glass makes up more than 1/8 of the non-empty voxels
+void derive_glass_flags(Shard& s) {
+  s.cert_auto = s.glass * 8 <= s.non_empty;
+  s.has_glass = s.glass > 0;
+}
+
 // Distance passes + packing + glass share on every device (canonical bytes already resident on
 // each, ordered on part[0]), then wait (upload is not a hot call).
 int volume_finish_all(vrt_ctx* ctx) {
@@ -704,10 +714,7 @@ int volume_finish_all(vrt_ctx* ctx) {
     VRT_HIP(ctx, hipSetDevice(s.device));
     const uint64_t vol = uint64_t(s.n) * s.n * s.n;
     vrt::launch_volume_passes(s.d_vox, s.d_tmp, s.d_vox_pad, uint32_t(s.n), s.octants, main_stream(s));
-    // certified walks cannot settle glass pixels (their secondary rays start at the exact hit
-    // point) and a glass pixel pays the certified primary walk before the exact path: the
-    // automatic mode turns them off when glass makes up more than 1/8 of the non-empty voxels
-    if (!s.d_vstats) VRT_HIP(ctx, hipMalloc(&s.d_vstats, 2 * sizeof(unsigned long long)));
+    if (!s.d_vstats) VRT_HIP(ctx, hipMalloc(&s.d_vstats, kVstatWords * sizeof(unsigned long long)));
     VRT_HIP(ctx, hipMemsetAsync(s.d_vstats, 0, 2 * sizeof(unsigned long long), main_stream(s)));
     vrt::launch_glass_share(s.d_vox, vol, s.d_vstats, main_stream(s));
     VRT_HIP(ctx, hipGetLastError());
@@ -717,8 +724,68 @@ int volume_finish_all(vrt_ctx* ctx) {
     unsigned long long vs[2] = {0, 0};
     VRT_HIP(ctx, hipMemcpyAsync(vs, s.d_vstats, sizeof(vs), hipMemcpyDeviceToHost, main_stream(s)));
     VRT_HIP(ctx, hipStreamSynchronize(main_stream(s)));
-    s.cert_auto = vs[0] * 8 <= vs[1];
-    s.has_glass = vs[0] > 0;
+    s.glass = vs[0];
+    s.non_empty = vs[1];
+    derive_glass_flags(s);
+  }
+  ctx->err.clear();
+  return VRT_OK;
+}
+
+// vrt_update_volume_region / _device: the box from the host (`host`) or from the first device
+// (`dev`, ordered on cs) to every device, which writes it into its canonical replica and rebuilds
+// the packed texels of the edit plan (launch_volume_edit_passes).
+int update_region_all(vrt_ctx* ctx, const int32_t origin[3], const int32_t extent[3], const uint8_t* host,
+                      const uint8_t* dev, hipStream_t cs) {
+  Shard& root = ctx->sh[0];
+  if (!root.d_vox_pad) return fail(ctx, VRT_ERR_NO_VOLUME, "no volume uploaded");
+  if (!origin || !extent || (!host && !dev)) return fail(ctx, VRT_ERR_INVALID, "null origin, extent or voxels");
+  for (int a = 0; a < 3; ++a) {
+    if (extent[a] <= 0) return fail(ctx, VRT_ERR_INVALID, "edit extent must be positive");
+    if (origin[a] < 0 || origin[a] >= root.n || extent[a] > root.n - origin[a])
+      return fail(ctx, VRT_ERR_INVALID, "edit box is not inside the volume");
+  }
+  const size_t bytes = size_t(extent[0]) * size_t(extent[1]) * size_t(extent[2]);
+  DeviceGuard guard;
+  // frames still in flight on the lanes read the packed volume (the upload's rule)
+  for (Shard& s : ctx->sh) {
+    VRT_HIP(ctx, hipSetDevice(s.device));
+    VRT_HIP(ctx, hipDeviceSynchronize());
+  }
+  if (dev) {
+    VRT_HIP(ctx, hipSetDevice(root.device));
+    VRT_HIP(ctx, hipEventRecord(root.ev_gs, cs));
+  }
+  // the box is staged at the head of d_tmp (bytes <= N^3), which the passes only write after the
+  // box write has read it
+  for (Shard& s : ctx->sh) {
+    VRT_HIP(ctx, hipSetDevice(s.device));
+    if (dev) {
+      VRT_HIP(ctx, hipStreamWaitEvent(main_stream(s), root.ev_gs, 0));
+      VRT_HIP(ctx, hipMemcpyPeerAsync(s.d_tmp, s.device, dev, root.device, bytes, main_stream(s)));
+    } else {
+      VRT_HIP(ctx, hipMemcpyAsync(s.d_tmp, host, bytes, hipMemcpyHostToDevice, main_stream(s)));
+    }
+    VRT_HIP(ctx, hipMemsetAsync(s.d_vstats, 0, kVstatWords * sizeof(unsigned long long), main_stream(s)));
+    vrt::launch_edit_apply(s.d_tmp, s.d_vox, uint32_t(s.n), origin, extent, s.d_vstats, main_stream(s));
+    VRT_HIP(ctx, hipGetLastError());
+  }
+  for (Shard& s : ctx->sh) {
+    VRT_HIP(ctx, hipSetDevice(s.device));
+    unsigned long long c[5] = {0, 0, 0, 0, 0};
+    VRT_HIP(ctx, hipMemcpyAsync(c, s.d_vstats, sizeof(c), hipMemcpyDeviceToHost, main_stream(s)));
+    VRT_HIP(ctx, hipStreamSynchronize(main_stream(s)));
+    s.glass = s.glass - c[0] + c[2];
+    s.non_empty = s.non_empty - c[1] + c[3];
+    derive_glass_flags(s);
+    // no cell became empty or occupied: every skip distance stands, only voxel bytes change
+    vrt::launch_volume_edit_passes(s.d_vox, s.d_tmp, s.d_vox_pad, uint32_t(s.n), s.octants, origin, extent,
+                                   c[4] != 0, main_stream(s));
+    VRT_HIP(ctx, hipGetLastError());
+  }
+  for (Shard& s : ctx->sh) {
+    VRT_HIP(ctx, hipSetDevice(s.device));
+    VRT_HIP(ctx, hipStreamSynchronize(main_stream(s)));
   }
   ctx->err.clear();
   return VRT_OK;
@@ -1270,6 +1337,27 @@ int vrt_upload_volume_device(vrt_ctx* ctx, const uint8_t* d_voxels, int32_t n, v
   VRT_HIP(ctx, hipStreamWaitEvent(main_stream(root), root.ev_gs, 0));
   if ((st = broadcast_volume(ctx)) != VRT_OK) return st;
   return volume_finish_all(ctx);
+}
+
+int vrt_update_volume_region(vrt_ctx* ctx, const int32_t origin[3], const int32_t extent[3], const uint8_t* voxels) {
+  if (!ctx) return VRT_ERR_INVALID;
+  if (!voxels) return fail(ctx, VRT_ERR_INVALID, "null voxels");
+  return update_region_all(ctx, origin, extent, voxels, nullptr, nullptr);
+}
+
+int vrt_update_volume_region_device(vrt_ctx* ctx, const int32_t origin[3], const int32_t extent[3],
+                                    const uint8_t* d_voxels, void* hip_stream) {
+  if (!ctx) return VRT_ERR_INVALID;
+  if (!d_voxels) return fail(ctx, VRT_ERR_INVALID, "null voxels");
+  return update_region_all(ctx, origin, extent, nullptr, d_voxels, static_cast<hipStream_t>(hip_stream));
+}
+
+int vrt_volume_edit_plan(int32_t n, int32_t octants, const int32_t origin[3], const int32_t extent[3], int32_t* out) {
+  if (!origin || !extent || !out || (octants != 8 && octants != 1) || n < 2 || n > 1024 || (n & (n - 1)) != 0)
+    return VRT_ERR_INVALID;
+  for (int a = 0; a < 3; ++a)
+    if (extent[a] <= 0 || origin[a] < 0 || origin[a] >= n || extent[a] > n - origin[a]) return VRT_ERR_INVALID;
+  return vrt::volume_edit_plan(n, octants, origin, extent, out);
 }
 
 int vrt_build_scene_device(vrt_ctx* ctx, int32_t scene, int32_t n, uint32_t seed, void* hip_stream) {

@@ -112,6 +112,19 @@ void launch_reduce_counters(unsigned long long* rep, unsigned long long* dst, hi
 // (octants == 8; tmp = 3 N^3 bytes) or one centred-distance volume (tmp = 2 N^3 bytes)
 void launch_volume_passes(const uint8_t* vox, uint8_t* tmp, uint16_t* packed, uint32_t n,
                           int octants, hipStream_t s);
+// in-place edit of the box [lo, lo + ext) (vrt_update_volume_region), inside [0, N)^3:
+// the packed texels an edit may change, per packed volume o: out[o*6 + 0..5] = {x0,y0,z0,x1,y1,z1}
+// (half-open, in [0, N)^3; host arithmetic)
+int volume_edit_plan(int32_t n, int octants, const int32_t lo[3], const int32_t ext[3], int32_t* out);
+// the box-local bytes `box` (device, x fastest) into the canonical volume; counts[0..4] (accumulating)
+// = the box's glass and non-empty voxels before, the same after, cells whose emptiness changed
+void launch_edit_apply(const uint8_t* box, uint8_t* vox, uint32_t n, const int32_t lo[3], const int32_t ext[3],
+                       unsigned long long* counts, hipStream_t s);
+// the packed volume(s) brought to the bytes of launch_volume_passes on the edited canonical volume by
+// region passes over the plan's boxes (tmp as there); distances = false (no cell's emptiness
+// changed): the voxel bytes of the box only
+void launch_volume_edit_passes(const uint8_t* vox, uint8_t* tmp, uint16_t* packed, uint32_t n, int octants,
+                               const int32_t lo[3], const int32_t ext[3], bool distances, hipStream_t s);
 // glass and non-empty voxel counts into out[0..1] (accumulating)
 void launch_glass_share(const uint8_t* vox, uint64_t total, unsigned long long* out, hipStream_t s);
 void launch_build_scene(uint8_t* vox, int scene, uint32_t n, const float* noise, hipStream_t s);

@@ -30,6 +30,7 @@
 #include "vrt_walk.h"
 #include "vrt_cert.h"
 #include "vrt_aux_kernels.h"
+#include "vrt_edit_kernels.h"
 
 namespace vrt {
 
@@ -757,6 +758,136 @@ void launch_volume_passes(const uint8_t* vox, uint8_t* tmp, uint16_t* packed, ui
     hipLaunchKernelGGL(dist_pass_kernel, dim3(b1), dim3(256), 0, s, da, db, n, 1, 0);
     hipLaunchKernelGGL(dist_pass_kernel, dim3(b1), dim3(256), 0, s, db, da, n, 2, 0);
     hipLaunchKernelGGL(pack_volume_kernel, dim3(b2), dim3(256), 0, s, vox, da, packed, n);
+  }
+}
+
+// ---- in-place edits (vrt_update_volume_region): the boxes of a regional rebuild -------------------
+namespace {
+
+struct Span {  // cells [a, b] of one axis, clipped to the volume
+  int32_t a, b;
+};
+Span clip_span(int64_t a, int64_t b, int32_t n) {
+  return Span{int32_t(std::max<int64_t>(a, 0)), int32_t(std::min<int64_t>(b, int64_t(n) - 1))};
+}
+// Edit cells [lo, hi) of an axis. An occupied cell kFwdCap or more cells ahead cannot lower a capped
+// F, so the anchors whose F can change lie up to kFwdCap - 1 cells behind the edit (against sg) ...
+Span fwd_anchors(int32_t lo, int32_t hi, int sg, int32_t n) {
+  const int64_t r = int64_t(kFwdCap) - 1;
+  return sg > 0 ? clip_span(lo - r, int64_t(hi) - 1, n) : clip_span(lo, int64_t(hi) - 1 + r, n);
+}
+// ... a pass over them reads its input up to kFwdCap - 1 cells ahead (the same cells for both signs) ...
+Span fwd_inputs(int32_t lo, int32_t hi, int32_t n) {
+  const int64_t r = int64_t(kFwdCap) - 1;
+  return clip_span(lo - r, int64_t(hi) - 1 + r, n);
+}
+// ... and G(w) = F(w - s) - 1 moves them one cell ahead: the packed texels (with the edit's own
+// cells, for the voxel bytes)
+Span fwd_texels(int32_t lo, int32_t hi, int sg, int32_t n) {
+  const int64_t r = int64_t(kFwdCap) - 1;
+  const int64_t a = (sg > 0 ? lo - r : int64_t(lo)) + sg, b = (sg > 0 ? int64_t(hi) - 1 : int64_t(hi) - 1 + r) + sg;
+  return clip_span(std::min<int64_t>(a, lo), std::max<int64_t>(b, int64_t(hi) - 1), n);
+}
+// the centred D (single layout): cells within `reach` of the edit
+Span dist_span(int32_t lo, int32_t hi, int64_t reach, int32_t n) {
+  return clip_span(lo - reach, int64_t(hi) - 1 + reach, n);
+}
+Region region_of(Span x, Span y, Span z) {
+  return Region{x.a, y.a, z.a, x.b - x.a + 1, y.b - y.a + 1, z.b - z.a + 1};
+}
+unsigned region_blocks(uint64_t cells) { return unsigned(std::min<uint64_t>((cells + 255) / 256, 16384)); }
+
+}  // namespace
+
+int volume_edit_plan(int32_t n, int octants, const int32_t lo[3], const int32_t ext[3], int32_t* out) {
+  for (int o = 0; o < octants; ++o)
+    for (int a = 0; a < 3; ++a) {
+      const int32_t hi = lo[a] + ext[a];
+      const Span t = octants == 8 ? fwd_texels(lo[a], hi, (o >> a & 1) ? -1 : 1, n)
+                                  : dist_span(lo[a], hi, int64_t(kDistCap) - 1, n);
+      out[o * 6 + a] = t.a;
+      out[o * 6 + 3 + a] = t.b + 1;
+    }
+  return octants;
+}
+
+void launch_edit_apply(const uint8_t* box, uint8_t* vox, uint32_t n, const int32_t lo[3], const int32_t ext[3],
+                       unsigned long long* counts, hipStream_t s) {
+  const Region b{lo[0], lo[1], lo[2], ext[0], ext[1], ext[2]};
+  hipLaunchKernelGGL(edit_apply_kernel, dim3(region_blocks(region_cells(b))), dim3(256), 0, s, box, vox, b, n,
+                     counts);
+}
+
+void launch_volume_edit_passes(const uint8_t* vox, uint8_t* tmp, uint16_t* packed, uint32_t n, int octants,
+                               const int32_t lo[3], const int32_t ext[3], bool distances, hipStream_t s) {
+  const int32_t ni = int32_t(n);
+  const int32_t hi[3] = {lo[0] + ext[0], lo[1] + ext[1], lo[2] + ext[2]};
+  const uint64_t vol = uint64_t(n) * n * n, pvol = uint64_t(n + 1) * (n + 1) * (n + 1);
+  const Region box{lo[0], lo[1], lo[2], ext[0], ext[1], ext[2]};
+  const Region whole{0, 0, 0, ni, ni, ni};
+  // region-local scratch: every box is clipped to the volume, so each fits N^3 bytes
+  uint8_t* da = tmp;
+  uint8_t* db = tmp + vol;
+  if (octants == 8) {
+    uint8_t* dc = tmp + 2 * vol;
+    const Span iy = fwd_inputs(lo[1], hi[1], ni), iz = fwd_inputs(lo[2], hi[2], ni);
+    for (int sx = 1; sx >= -1; sx -= 2) {
+      const Span ax = fwd_anchors(lo[0], hi[0], sx, ni);
+      const Region rx = region_of(ax, iy, iz);  // x pass: the y and z passes' inputs
+      if (distances)
+        hipLaunchKernelGGL(fwd_pass_region_kernel, dim3(region_blocks(region_cells(rx))), dim3(256), 0, s, vox,
+                           whole, da, rx, n, 0, sx, 1);
+      for (int sy = 1; sy >= -1; sy -= 2) {
+        const Span ay = fwd_anchors(lo[1], hi[1], sy, ni);
+        const Region ry = region_of(ax, ay, iz);
+        if (distances)
+          hipLaunchKernelGGL(fwd_pass_region_kernel, dim3(region_blocks(region_cells(ry))), dim3(256), 0, s, da,
+                             rx, db, ry, n, 1, sy, 0);
+        for (int sz = 1; sz >= -1; sz -= 2) {
+          const Span az = fwd_anchors(lo[2], hi[2], sz, ni);
+          const Region rz = region_of(ax, ay, az);
+          const int o = (sx < 0 ? 1 : 0) | (sy < 0 ? 2 : 0) | (sz < 0 ? 4 : 0);
+          uint16_t* dst = packed + size_t(o) * pvol;
+          if (distances) {
+            hipLaunchKernelGGL(fwd_pass_region_kernel, dim3(region_blocks(region_cells(rz))), dim3(256), 0, s, db,
+                               ry, dc, rz, n, 2, sz, 0);
+            const Region pb = region_of(fwd_texels(lo[0], hi[0], sx, ni), fwd_texels(lo[1], hi[1], sy, ni),
+                                        fwd_texels(lo[2], hi[2], sz, ni));
+            hipLaunchKernelGGL(fwd_pack_region_kernel, dim3(region_blocks(region_cells(pb))), dim3(256), 0, s, vox,
+                               dc, rz, dst, pb, n, sx, sy, sz);
+          } else {
+            hipLaunchKernelGGL(fwd_pack_region_kernel, dim3(region_blocks(region_cells(box))), dim3(256), 0, s, vox,
+                               static_cast<const uint8_t*>(nullptr), box, dst, box, n, sx, sy, sz);
+          }
+        }
+      }
+    }
+  } else if (distances) {
+    const int64_t r1 = int64_t(kDistCap) - 1;
+    const Span ax = dist_span(lo[0], hi[0], r1, ni), ay = dist_span(lo[1], hi[1], r1, ni);
+    const Span az = dist_span(lo[2], hi[2], r1, ni);
+    // the z pass reads y-pass values kDistCap - 1 cells to both sides in z, the y pass x-pass values in y
+    const Span iy = dist_span(lo[1], hi[1], 2 * r1, ni), iz = dist_span(lo[2], hi[2], 2 * r1, ni);
+    const Region rx = region_of(ax, iy, iz), ry = region_of(ax, ay, iz), rz = region_of(ax, ay, az);
+    hipLaunchKernelGGL(dist_pass_region_kernel, dim3(region_blocks(region_cells(rx))), dim3(256), 0, s, vox, whole,
+                       da, rx, n, 0, 1);
+    hipLaunchKernelGGL(dist_pass_region_kernel, dim3(region_blocks(region_cells(ry))), dim3(256), 0, s, da, rx, db,
+                       ry, n, 1, 0);
+    hipLaunchKernelGGL(dist_pass_region_kernel, dim3(region_blocks(region_cells(rz))), dim3(256), 0, s, db, ry, da,
+                       rz, n, 2, 0);
+    hipLaunchKernelGGL(pack_volume_region_kernel, dim3(region_blocks(region_cells(rz))), dim3(256), 0, s, vox, da,
+                       rz, packed, rz, n);
+  } else {
+    hipLaunchKernelGGL(pack_volume_region_kernel, dim3(region_blocks(region_cells(box))), dim3(256), 0, s, vox,
+                       static_cast<const uint8_t*>(nullptr), box, packed, box, n);
+  }
+  // texel N of an axis repeats voxel 0: rewritten when the box holds coordinate 0 of that axis
+  const int wrap = (lo[0] == 0 ? 1 : 0) | (lo[1] == 0 ? 2 : 0) | (lo[2] == 0 ? 4 : 0);
+  if (wrap) {
+    const uint64_t cells = uint64_t(ext[0] + (wrap & 1)) * uint64_t(ext[1] + (wrap >> 1 & 1)) *
+                           uint64_t(ext[2] + (wrap >> 2 & 1));
+    hipLaunchKernelGGL(edge_pack_region_kernel, dim3(region_blocks(cells)), dim3(256), 0, s, vox, packed, pvol,
+                       octants, box, wrap, n);
   }
 }
 
