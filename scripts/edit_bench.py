@@ -4,8 +4,8 @@
 Per scene (terrain 512^3, refraction 128^3) and edit size (one voxel, 16^3), two arms alternate, each
 bringing the resident volume to the same edited state:
   edit: vrt_update_volume_region_device of the box (the regional rebuild);
-  full: vrt_upload_volume_device of the whole edited volume (every pass over N^3: the only route
-        before the edit entry points, and unchanged code).
+  full: vrt_upload_volume_device of the whole edited volume (the same kernels over the box [0, N)^3:
+        every pass over N^3, every texel packed).
 Both calls end synchronised, so a host clock around them is the cost a caller pays. Successive
 iterations toggle the box between its original bytes and their emptiness-inverted bytes, so every
 edit changes emptiness and runs the distance passes. Reported: the median of --reps timings after
@@ -64,9 +64,10 @@ def edit_visits(n, octants, origin, extent):
 
 
 def full_visits(n, octants):
+    edge = (n + 1) ** 3 - n ** 3   # plane N of every axis: one visit writes the texel of all packed volumes
     if octants == 8:
-        return {"x": 2 * n ** 3, "y": 4 * n ** 3, "z": 8 * n ** 3, "pack": 8 * (n + 1) ** 3}
-    return {"x": n ** 3, "y": n ** 3, "z": n ** 3, "pack": (n + 1) ** 3}
+        return {"x": 2 * n ** 3, "y": 4 * n ** 3, "z": 8 * n ** 3, "pack": 8 * n ** 3 + edge}
+    return {"x": n ** 3, "y": n ** 3, "z": n ** 3, "pack": n ** 3 + edge}
 
 
 def main():

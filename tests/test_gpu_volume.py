@@ -9,58 +9,9 @@ import numpy as np
 import pytest
 
 import voxelraytracer_amd as vrt
+from skipfield_reference import chebyshev_reference, forward_reference, packed_reference
 
 pytestmark = pytest.mark.gpu
-CAP = 64  # kDistCap of csrc/vrt_walk.h
-FWD_CAP = 128  # kFwdCap (VRT_FWD_CAP, csrc/vrt_tuning.h)
-
-
-def forward_reference(vox, n, octant):
-    """G of `octant` ([z][y][x] n^3) by brute force: in coordinates flipped so that the octant's
-    step is +1 on every axis, F(v) = the largest E with v + E <= n and the box [v, v+E-1]^3
-    empty (prefix-sum box counts), G(v) = F(v - 1) - 1 clamped at 0 (0 on the low faces)."""
-    sl = tuple(slice(None, None, -1) if octant >> a & 1 else slice(None) for a in (2, 1, 0))
-    occ = (vox.reshape(n, n, n) != 0)[sl].astype(np.int64)
-    c = np.zeros((n + 1,) * 3, np.int64)
-    c[1:, 1:, 1:] = occ.cumsum(0).cumsum(1).cumsum(2)
-    f = np.zeros((n, n, n), np.int64)
-    for e in range(1, min(FWD_CAP, n) + 1):
-        m = n - e + 1   # anchors with v + e <= n on every axis
-        i0 = np.arange(m)
-        z0, y0, x0 = i0[:, None, None], i0[None, :, None], i0[None, None, :]
-        z1, y1, x1 = z0 + e, y0 + e, x0 + e
-        cnt = (c[z1, y1, x1] - c[z0, y1, x1] - c[z1, y0, x1] - c[z1, y1, x0] + c[z0, y0, x1]
-               + c[z0, y1, x0] + c[z1, y0, x0] - c[z0, y0, x0])
-        sub = f[:m, :m, :m]
-        f[:m, :m, :m] = np.where(cnt == 0, e, sub)
-    g = np.zeros((n, n, n), np.int64)
-    g[1:, 1:, 1:] = np.maximum(f[:-1, :-1, :-1] - 1, 0)
-    return g[sl]
-
-
-def chebyshev_reference(vox, n):
-    occ = np.zeros((n + 2,) * 3, bool)   # [z][y][x] with a non-empty border at -1 and n
-    occ[0, :, :] = occ[-1, :, :] = occ[:, 0, :] = occ[:, -1, :] = occ[:, :, 0] = occ[:, :, -1] = True
-    occ[1:-1, 1:-1, 1:-1] = vox.reshape(n, n, n) != 0
-    d = np.full((n, n, n), CAP, np.int32)
-    for r in range(CAP - 1, -1, -1):   # smallest r with a non-empty voxel in the (2r+1)^3 box
-        k = 2 * r + 1
-        # box-OR via cumulative sums
-        c = np.pad(occ.astype(np.int32), ((1, 0), (1, 0), (1, 0))).cumsum(0).cumsum(1).cumsum(2)
-        lo = 1 - r + 1   # index shift: occ index i+1 = voxel i, padded once more for cumsum
-        hi = lo + k
-        idx = np.arange(n)
-
-        def box(a):
-            z0, z1 = idx[:, None, None] + lo - 1, idx[:, None, None] + hi - 1
-            y0, y1 = idx[None, :, None] + lo - 1, idx[None, :, None] + hi - 1
-            x0, x1 = idx[None, None, :] + lo - 1, idx[None, None, :] + hi - 1
-            z0, z1, y0, y1, x0, x1 = [np.clip(v, 0, n + 2) for v in (z0, z1, y0, y1, x0, x1)]
-            return (a[z1, y1, x1] - a[z0, y1, x1] - a[z1, y0, x1] - a[z1, y1, x0] + a[z0, y0, x1]
-                    + a[z0, y1, x0] + a[z1, y0, x0] - a[z0, y0, x0])
-
-        d = np.where(box(c) > 0, r, d)
-    return d
 
 
 @pytest.mark.parametrize("scene,n", [("terrain", 16), ("glass_cube", 16), ("refraction", 32),
@@ -106,6 +57,32 @@ def test_single_layout_centred_distance(built, scene, n):
     assert np.array_equal(packed[:n, :n, :n] & 0xFF, vox.reshape(n, n, n))
     assert np.all(packed[n] >> 8 == 0) and np.all(packed[:, n] >> 8 == 0)
     assert np.array_equal(packed[:n, :n, :n] >> 8, chebyshev_reference(vox, n))
+
+
+@pytest.mark.parametrize("layout", [8, 1])
+@pytest.mark.parametrize("n", [2, 4, 8])
+def test_smallest_volumes(built, n, layout):
+    """Random bytes (0..3, about half empty) at the smallest edges, both layouts, every texel of
+    the (N+1)^3 volumes against the NumPy reference. At n = 2 every texel neighbours plane N and
+    every scan is cut by a volume face: the whole-volume boxes of the upload clip on every side."""
+    rng = np.random.default_rng(n)
+    vox = np.where(rng.random(n ** 3) < 0.5, 0, rng.integers(1, 4, n ** 3)).astype(np.uint8)
+    assert 0 < np.count_nonzero(vox) < n ** 3
+    with vrt.Renderer(0) as r:
+        r.set_skip_layout(layout)
+        r.upload_volume(vox, n)
+        vols = r.debug_packed_volume()
+    assert vols.shape == (layout,) + (n + 1,) * 3
+    v = vox.reshape(n, n, n)
+    for packed in vols:
+        assert np.array_equal(packed[n, :n, :n] & 0xFF, v[0])        # plane z = N repeats z = 0
+        assert np.array_equal(packed[:n, n, :n] & 0xFF, v[:, 0])
+        assert np.array_equal(packed[:n, :n, n] & 0xFF, v[:, :, 0])
+        assert packed[n, n, n] & 0xFF == v[0, 0, 0]
+        assert np.all(packed[n] >> 8 == 0) and np.all(packed[:, n] >> 8 == 0)
+        assert np.all(packed[:, :, n] >> 8 == 0)
+    want = packed_reference(vox, n, layout)
+    assert np.array_equal(vols, want), np.argwhere(vols != want)[:4].tolist()
 
 
 @pytest.mark.parametrize("scene,n,w,h,rt", [("terrain", 64, 160, 90, (4, 2)),

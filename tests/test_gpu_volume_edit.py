@@ -1,8 +1,10 @@
-"""In-place voxel edits (GPU): vrt_update_volume_region rebuilds only the packed texels of its plan
-(region forms of the distance passes and packs, csrc/vrt_edit_kernels.h), and the result must be, byte
-for byte, what a full upload of the edited volume produces. The reference is always a fresh Renderer
-with a full upload_volume of the edited bytes: its debug_packed_volume() must be array_equal, its
-frames bit-identical, its certified() the same."""
+"""In-place voxel edits (GPU): vrt_update_volume_region rebuilds only the packed texels of its plan, by
+the kernels that build the whole skip field for an upload (csrc/vrt_skipfield_kernels.h) run on the
+plan's boxes, and the result must be, byte for byte, what a full upload of the edited volume produces.
+The reference is a fresh Renderer with a full upload_volume of the edited bytes (its
+debug_packed_volume() must be array_equal, its frames bit-identical, its certified() the same) and,
+since upload and edit share their kernels, the brute-force NumPy transform of
+tests/skipfield_reference.py on small volumes."""
 import ctypes as C
 import os
 
@@ -11,20 +13,13 @@ import pytest
 
 import oracle
 import voxelraytracer_amd as vrt
+from skipfield_reference import apply_edit, packed_reference, random_edit
 from voxelraytracer_amd import abi
 
 pytestmark = pytest.mark.gpu
 
 COLOR_TOL = 1e-4   # the project's colour tolerance against the oracle (tests/test_gpu_parity.py)
 THREADS = min(16, os.cpu_count() or 1)
-
-
-def apply_edit(vox, n, origin, block):
-    """The edited copy of the n^3 bytes: `block` [z][y][x] at origin (x, y, z)."""
-    out = vox.reshape(n, n, n).copy()
-    ez, ey, ex = block.shape
-    out[origin[2]:origin[2] + ez, origin[1]:origin[1] + ey, origin[0]:origin[0] + ex] = block
-    return out.reshape(-1)
 
 
 def current_block(vox, n, origin, extent):
@@ -118,6 +113,33 @@ def test_edit_sequence_single_layout(built):
             r.update_volume(origin, block)
             if i in (0, 7):
                 assert_same_packed(r.debug_packed_volume(), fresh_packed(states[i], n, 1))
+
+
+@pytest.mark.parametrize("layout", [8, 1])
+@pytest.mark.parametrize("scene,n,seed", [("terrain", 16, 3), ("refraction", 16, 2), ("glass_cube", 16, 7),
+                                          ("terrain", 32, 10), ("refraction", 32, 11)])
+def test_edits_match_the_numpy_reference(built, scene, n, seed, layout):
+    """Upload and edit run the same kernels, so an edit is also held against the independent NumPy
+    transform: the four seeded edits of tests/test_volume_edit_plan.py (each changes emptiness), then a
+    box on x = y = z = 0 with its emptiness inverted (plane N, corner texel included); after every
+    edit every texel of the (N+1)^3 volume(s) equals the reference of the edited bytes."""
+    rng = np.random.default_rng(seed)
+    vox = vrt.build_scene(scene, n)
+    with vrt.Renderer(0) as r:
+        r.set_skip_layout(layout)
+        r.upload_volume(vox, n)
+        assert r._lib.vrt_volume_octants(r._h) == layout
+        for i in range(5):
+            if i < 4:
+                origin, block = random_edit(rng, n)
+            else:
+                origin = (0, 0, 0)
+                block = np.where(current_block(vox, n, origin, (4, 3, 2)) != 0, 0, 3).astype(np.uint8)
+            new = apply_edit(vox, n, origin, block)
+            assert np.any((new != 0) != (vox != 0)), "the edit changes no emptiness"
+            vox = new
+            r.update_volume(origin, block)
+            assert_same_packed(r.debug_packed_volume(), packed_reference(vox, n, layout))
 
 
 @pytest.mark.parametrize("n,layout,probe", [(256, 8, (200, 200, 200)), (128, 1, (100, 100, 100))])

@@ -1,6 +1,6 @@
 // vrt_aux_kernels.h — the kernels beside the frame: glass share, scene build, band assembly, RGB8 pack,
-// randomize, counter reduce, the distance / forward-distance passes and packs, the fast-math check.
-// Includes vrt_internal.h, vrt_math.h and vrt_walk.h (kDistCap, the packed texel layout).
+// randomize, counter reduce, the fast-math check. (The skip field of the packed volume is built by
+// vrt_skipfield_kernels.h.) Includes vrt_internal.h, vrt_math.h and vrt_walk.h.
 #ifndef VRT_AUX_KERNELS_H
 #define VRT_AUX_KERNELS_H
 
@@ -157,106 +157,6 @@ __global__ void __launch_bounds__(64) reduce_counters_kernel(unsigned long long*
   }
   dst[q] += s;
 }
-
-
-// Chebyshev distance field, one separable pass per axis (x, then y, then z), capped at
-// kDistCap: out(v) = min(kDistCap, distance to the boundary pseudo-voxels -1 and N on this axis,
-// min over |o| < kDistCap of max(|o|, in(v + o e_axis))), where the x pass reads in = 0 for a
-// non-empty voxel and kDistCap otherwise. The composition is the exact L-inf distance transform
-// (capped), so D(v) >= 1 guarantees an empty box of half-width D-1 around v inside the volume.
-__global__ void __launch_bounds__(256) dist_pass_kernel(const uint8_t* __restrict__ in,
-                                                        uint8_t* __restrict__ out, uint32_t n,
-                                                        int axis, int first) {
-  const uint64_t total = uint64_t(n) * n * n;
-  const uint64_t stride = axis == 0 ? 1u : (axis == 1 ? uint64_t(n) : uint64_t(n) * n);
-  for (uint64_t q = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; q < total;
-       q += uint64_t(gridDim.x) * blockDim.x) {
-    const uint32_t coord = uint32_t((q / stride) % n);
-    uint32_t d = min(min(coord + 1u, n - coord), kDistCap);
-    for (uint32_t o = 0; o < kDistCap && o < d; ++o) {
-      // neighbours at offset -o and +o along the axis
-      for (int sgn = -1; sgn <= 1; sgn += 2) {
-        if (o == 0 && sgn > 0) break;
-        const int64_t cc = int64_t(coord) + sgn * int64_t(o);
-        if (cc < 0 || cc >= int64_t(n)) continue;
-        const uint8_t v = in[uint64_t(int64_t(q) + (cc - int64_t(coord)) * int64_t(stride))];
-        const uint32_t val = first ? (v != 0 ? 0u : kDistCap) : uint32_t(v);
-        d = min(d, max(o, val));
-      }
-    }
-    out[q] = uint8_t(d);
-  }
-}
-
-// Pack into the kernel's padded (N+1)^3 format: voxel | D << 8, plane N repeats plane 0 (GL_REPEAT
-// folded into the layout) with D = 0 there (those texels are only read at c == N exactly).
-// Single-volume layout (N = 1024).
-__global__ void __launch_bounds__(256) pack_volume_kernel(const uint8_t* __restrict__ src,
-                                                          const uint8_t* __restrict__ dist,
-                                                          uint16_t* __restrict__ dst, uint32_t n) {
-  const uint32_t p = n + 1u;
-  const uint64_t total = uint64_t(p) * p * p;
-  for (uint64_t q = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; q < total;
-       q += uint64_t(gridDim.x) * blockDim.x) {
-    const uint32_t i = uint32_t(q % p), j = uint32_t((q / p) % p), k = uint32_t(q / (uint64_t(p) * p));
-    const bool edge = i == n || j == n || k == n;
-    const uint32_t si = i == n ? 0u : i, sj = j == n ? 0u : j, sk = k == n ? 0u : k;
-    const uint64_t sq = si + (uint64_t(sj) + uint64_t(sk) * n) * n;
-    dst[q] = uint16_t(src[sq] | (edge ? 0u : uint32_t(dist[sq]) << 8));
-  }
-}
-
-// One-sided pass of the octant forward distance along `axis` in direction sg = +-1:
-// out(v) = min(kFwdCap, distance to the outside pseudo-voxel ahead (N - c or c + 1),
-//              min over 0 <= o of max(o, in(v + sg*o*e_axis))),
-// where the first (x) pass reads in = 0 for a non-empty voxel and kFwdCap otherwise. x, then y,
-// then z: F(v) = min over non-empty / outside u in v's forward octant of max_a |u_a - v_a| (max
-// and min commute through the passes), i.e. the edge of the largest empty in-volume cube
-// anchored at v and extending along (sx, sy, sz). max(o, .) >= o, so the scan stops at o = d.
-__global__ void __launch_bounds__(256) fwd_pass_kernel(const uint8_t* __restrict__ in,
-                                                       uint8_t* __restrict__ out, uint32_t n,
-                                                       int axis, int sg, int first) {
-  const uint64_t total = uint64_t(n) * n * n;
-  const uint64_t stride = axis == 0 ? 1u : (axis == 1 ? uint64_t(n) : uint64_t(n) * n);
-  const int64_t step = sg > 0 ? int64_t(stride) : -int64_t(stride);
-  for (uint64_t q = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; q < total;
-       q += uint64_t(gridDim.x) * blockDim.x) {
-    const uint32_t coord = uint32_t((q / stride) % n);
-    uint32_t d = min(sg > 0 ? n - coord : coord + 1u, kFwdCap);
-    // o < d <= the outside distance keeps v + sg*o inside the volume
-    for (uint32_t o = 0; o < d; ++o) {
-      const uint8_t v = in[uint64_t(int64_t(q) + int64_t(o) * step)];
-      const uint32_t val = first ? (v != 0 ? 0u : kFwdCap) : uint32_t(v);
-      d = min(d, max(o, val));
-    }
-    out[q] = uint8_t(d);
-  }
-}
-
-// Pack octant (sx, sy, sz)'s padded (N+1)^3 volume: voxel | G << 8 with G(v) = F(v - s) - 1
-// (0 when v - s is outside or F(v - s) = 0), plane N a copy of plane 0 with G = 0.
-__global__ void __launch_bounds__(256) fwd_pack_kernel(const uint8_t* __restrict__ src,
-                                                       const uint8_t* __restrict__ fwd,
-                                                       uint16_t* __restrict__ dst, uint32_t n,
-                                                       int sx, int sy, int sz) {
-  const uint32_t p = n + 1u;
-  const uint64_t total = uint64_t(p) * p * p;
-  for (uint64_t q = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; q < total;
-       q += uint64_t(gridDim.x) * blockDim.x) {
-    const uint32_t i = uint32_t(q % p), j = uint32_t((q / p) % p), k = uint32_t(q / (uint64_t(p) * p));
-    const bool edge = i == n || j == n || k == n;
-    const uint32_t si = i == n ? 0u : i, sj = j == n ? 0u : j, sk = k == n ? 0u : k;
-    const uint64_t sq = si + (uint64_t(sj) + uint64_t(sk) * n) * n;
-    uint32_t g = 0;
-    const int64_t a = int64_t(i) - sx, b = int64_t(j) - sy, c = int64_t(k) - sz;
-    if (!edge && a >= 0 && b >= 0 && c >= 0 && a < int64_t(n) && b < int64_t(n) && c < int64_t(n)) {
-      const uint32_t f = fwd[uint64_t(a) + (uint64_t(b) + uint64_t(c) * n) * n];
-      g = f > 0u ? f - 1u : 0u;
-    }
-    dst[q] = uint16_t(src[sq] | (g << 8));
-  }
-}
-
 
 // Diagnostic (vrt_debug_fast_math): every float bit pattern, rcp_newton against the IEEE
 // division. out: {patterns with rcp_rn_ok, their mismatches, mismatches of normal-range patterns

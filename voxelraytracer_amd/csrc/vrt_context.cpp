@@ -713,7 +713,10 @@ int volume_finish_all(vrt_ctx* ctx) {
   for (Shard& s : ctx->sh) {
     VRT_HIP(ctx, hipSetDevice(s.device));
     const uint64_t vol = uint64_t(s.n) * s.n * s.n;
-    vrt::launch_volume_passes(s.d_vox, s.d_tmp, s.d_vox_pad, uint32_t(s.n), s.octants, main_stream(s));
+    // the whole volume as one edit box: every texel of the packed volume(s) is rebuilt
+    const int32_t origin[3] = {0, 0, 0}, extent[3] = {s.n, s.n, s.n};
+    vrt::launch_volume_edit_passes(s.d_vox, s.d_tmp, s.d_vox_pad, uint32_t(s.n), s.octants, origin, extent, true,
+                                   main_stream(s));
     if (!s.d_vstats) VRT_HIP(ctx, hipMalloc(&s.d_vstats, kVstatWords * sizeof(unsigned long long)));
     VRT_HIP(ctx, hipMemsetAsync(s.d_vstats, 0, 2 * sizeof(unsigned long long), main_stream(s)));
     vrt::launch_glass_share(s.d_vox, vol, s.d_vstats, main_stream(s));

@@ -108,10 +108,6 @@ void launch_render(const KArgs& a, bool stats, const uint16_t* vox, float4* out,
                    hipEvent_t ev_end = nullptr);
 // fold the counter replicas into dst (accumulating) and re-zero them
 void launch_reduce_counters(unsigned long long* rep, unsigned long long* dst, hipStream_t s);
-// the kernel's packed volume from the canonical N^3 bytes: 8 octant forward-distance volumes
-// (octants == 8; tmp = 3 N^3 bytes) or one centred-distance volume (tmp = 2 N^3 bytes)
-void launch_volume_passes(const uint8_t* vox, uint8_t* tmp, uint16_t* packed, uint32_t n,
-                          int octants, hipStream_t s);
 // in-place edit of the box [lo, lo + ext) (vrt_update_volume_region), inside [0, N)^3:
 // the packed texels an edit may change, per packed volume o: out[o*6 + 0..5] = {x0,y0,z0,x1,y1,z1}
 // (half-open, in [0, N)^3; host arithmetic)
@@ -120,9 +116,11 @@ int volume_edit_plan(int32_t n, int octants, const int32_t lo[3], const int32_t 
 // = the box's glass and non-empty voxels before, the same after, cells whose emptiness changed
 void launch_edit_apply(const uint8_t* box, uint8_t* vox, uint32_t n, const int32_t lo[3], const int32_t ext[3],
                        unsigned long long* counts, hipStream_t s);
-// the packed volume(s) brought to the bytes of launch_volume_passes on the edited canonical volume by
-// region passes over the plan's boxes (tmp as there); distances = false (no cell's emptiness
-// changed): the voxel bytes of the box only
+// the kernel's packed volume(s) from the canonical N^3 bytes after a change inside the box [lo, lo + ext):
+// 8 octant forward-distance volumes (octants == 8; tmp = 3 N^3 bytes) or one centred-distance volume
+// (tmp = 2 N^3 bytes), rebuilt by passes over the plan's boxes. An upload is the box [0, N)^3 (every
+// texel, plane N included); distances = false (no cell's emptiness changed): the voxel bytes of the
+// box only
 void launch_volume_edit_passes(const uint8_t* vox, uint8_t* tmp, uint16_t* packed, uint32_t n, int octants,
                                const int32_t lo[3], const int32_t ext[3], bool distances, hipStream_t s);
 // glass and non-empty voxel counts into out[0..1] (accumulating)

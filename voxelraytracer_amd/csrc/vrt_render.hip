@@ -30,7 +30,7 @@
 #include "vrt_walk.h"
 #include "vrt_cert.h"
 #include "vrt_aux_kernels.h"
-#include "vrt_edit_kernels.h"
+#include "vrt_skipfield_kernels.h"
 
 namespace vrt {
 
@@ -663,8 +663,11 @@ __global__ void __launch_bounds__(64, WAVES) exact_pass_kernel(KArgs a, const ui
 }
 
 // ------------------------------------------------------------------------------- launches --
-// Host wrappers of the kernels above and of vrt_aux_kernels.h (vrt_internal.h); the C-ABI context
-// is vrt_context.cpp.
+// Host wrappers of the kernels above, of vrt_aux_kernels.h and of vrt_skipfield_kernels.h
+// (vrt_internal.h); the C-ABI context is vrt_context.cpp.
+
+// workgroups of 256 for a grid-stride loop over `items`
+static unsigned grid_blocks(uint64_t items) { return unsigned(std::min<uint64_t>((items + 255) / 256, 16384)); }
 
 void launch_render(const KArgs& a, bool stats, const uint16_t* vox, float4* out, vrt_hit* hit,
                    unsigned long long* cnt_rep, hipStream_t s, hipEvent_t ev_begin, hipEvent_t ev_end) {
@@ -731,37 +734,7 @@ void launch_reduce_counters(unsigned long long* rep, unsigned long long* dst, hi
   hipLaunchKernelGGL(reduce_counters_kernel, dim3(1), dim3(64), 0, s, rep, dst);
 }
 
-void launch_volume_passes(const uint8_t* vox, uint8_t* tmp, uint16_t* packed, uint32_t n,
-                          int octants, hipStream_t s) {
-  const uint64_t vol = uint64_t(n) * n * n, pvol = uint64_t(n + 1) * (n + 1) * (n + 1);
-  const unsigned b1 = unsigned(std::min<uint64_t>((vol + 255) / 256, 16384));
-  const unsigned b2 = unsigned(std::min<uint64_t>((pvol + 255) / 256, 16384));
-  uint8_t* da = tmp;
-  uint8_t* db = tmp + vol;
-  if (octants == 8) {
-    // octant forward distances: 2 x passes, 4 y passes, 8 z passes + packs (x -> y -> z nesting)
-    uint8_t* dc = tmp + 2 * vol;
-    for (int sx = 1; sx >= -1; sx -= 2) {
-      hipLaunchKernelGGL(fwd_pass_kernel, dim3(b1), dim3(256), 0, s, vox, da, n, 0, sx, 1);
-      for (int sy = 1; sy >= -1; sy -= 2) {
-        hipLaunchKernelGGL(fwd_pass_kernel, dim3(b1), dim3(256), 0, s, da, db, n, 1, sy, 0);
-        for (int sz = 1; sz >= -1; sz -= 2) {
-          hipLaunchKernelGGL(fwd_pass_kernel, dim3(b1), dim3(256), 0, s, db, dc, n, 2, sz, 0);
-          const int o = (sx < 0 ? 1 : 0) | (sy < 0 ? 2 : 0) | (sz < 0 ? 4 : 0);
-          hipLaunchKernelGGL(fwd_pack_kernel, dim3(b2), dim3(256), 0, s, vox, dc,
-                             packed + size_t(o) * pvol, n, sx, sy, sz);
-        }
-      }
-    }
-  } else {
-    hipLaunchKernelGGL(dist_pass_kernel, dim3(b1), dim3(256), 0, s, vox, da, n, 0, 1);
-    hipLaunchKernelGGL(dist_pass_kernel, dim3(b1), dim3(256), 0, s, da, db, n, 1, 0);
-    hipLaunchKernelGGL(dist_pass_kernel, dim3(b1), dim3(256), 0, s, db, da, n, 2, 0);
-    hipLaunchKernelGGL(pack_volume_kernel, dim3(b2), dim3(256), 0, s, vox, da, packed, n);
-  }
-}
-
-// ---- in-place edits (vrt_update_volume_region): the boxes of a regional rebuild -------------------
+// ---- the skip field (upload, vrt_update_volume_region): the boxes of a regional rebuild ------------
 namespace {
 
 struct Span {  // cells [a, b] of one axis, clipped to the volume
@@ -795,7 +768,6 @@ Span dist_span(int32_t lo, int32_t hi, int64_t reach, int32_t n) {
 Region region_of(Span x, Span y, Span z) {
   return Region{x.a, y.a, z.a, x.b - x.a + 1, y.b - y.a + 1, z.b - z.a + 1};
 }
-unsigned region_blocks(uint64_t cells) { return unsigned(std::min<uint64_t>((cells + 255) / 256, 16384)); }
 
 }  // namespace
 
@@ -814,7 +786,7 @@ int volume_edit_plan(int32_t n, int octants, const int32_t lo[3], const int32_t 
 void launch_edit_apply(const uint8_t* box, uint8_t* vox, uint32_t n, const int32_t lo[3], const int32_t ext[3],
                        unsigned long long* counts, hipStream_t s) {
   const Region b{lo[0], lo[1], lo[2], ext[0], ext[1], ext[2]};
-  hipLaunchKernelGGL(edit_apply_kernel, dim3(region_blocks(region_cells(b))), dim3(256), 0, s, box, vox, b, n,
+  hipLaunchKernelGGL(edit_apply_kernel, dim3(grid_blocks(region_cells(b))), dim3(256), 0, s, box, vox, b, n,
                      counts);
 }
 
@@ -825,23 +797,25 @@ void launch_volume_edit_passes(const uint8_t* vox, uint8_t* tmp, uint16_t* packe
   const uint64_t vol = uint64_t(n) * n * n, pvol = uint64_t(n + 1) * (n + 1) * (n + 1);
   const Region box{lo[0], lo[1], lo[2], ext[0], ext[1], ext[2]};
   const Region whole{0, 0, 0, ni, ni, ni};
-  // region-local scratch: every box is clipped to the volume, so each fits N^3 bytes
+  // region-local scratch: every box is clipped to the volume, so each fits N^3 bytes. For an upload
+  // (lo = 0, ext = N on every axis) every span clips to [0, N - 1] and every box below is `whole`.
   uint8_t* da = tmp;
   uint8_t* db = tmp + vol;
   if (octants == 8) {
+    // octant forward distances: 2 x passes, 4 y passes, 8 z passes + packs (x -> y -> z nesting)
     uint8_t* dc = tmp + 2 * vol;
     const Span iy = fwd_inputs(lo[1], hi[1], ni), iz = fwd_inputs(lo[2], hi[2], ni);
     for (int sx = 1; sx >= -1; sx -= 2) {
       const Span ax = fwd_anchors(lo[0], hi[0], sx, ni);
       const Region rx = region_of(ax, iy, iz);  // x pass: the y and z passes' inputs
       if (distances)
-        hipLaunchKernelGGL(fwd_pass_region_kernel, dim3(region_blocks(region_cells(rx))), dim3(256), 0, s, vox,
+        hipLaunchKernelGGL(fwd_pass_kernel, dim3(grid_blocks(region_cells(rx))), dim3(256), 0, s, vox,
                            whole, da, rx, n, 0, sx, 1);
       for (int sy = 1; sy >= -1; sy -= 2) {
         const Span ay = fwd_anchors(lo[1], hi[1], sy, ni);
         const Region ry = region_of(ax, ay, iz);
         if (distances)
-          hipLaunchKernelGGL(fwd_pass_region_kernel, dim3(region_blocks(region_cells(ry))), dim3(256), 0, s, da,
+          hipLaunchKernelGGL(fwd_pass_kernel, dim3(grid_blocks(region_cells(ry))), dim3(256), 0, s, da,
                              rx, db, ry, n, 1, sy, 0);
         for (int sz = 1; sz >= -1; sz -= 2) {
           const Span az = fwd_anchors(lo[2], hi[2], sz, ni);
@@ -849,14 +823,14 @@ void launch_volume_edit_passes(const uint8_t* vox, uint8_t* tmp, uint16_t* packe
           const int o = (sx < 0 ? 1 : 0) | (sy < 0 ? 2 : 0) | (sz < 0 ? 4 : 0);
           uint16_t* dst = packed + size_t(o) * pvol;
           if (distances) {
-            hipLaunchKernelGGL(fwd_pass_region_kernel, dim3(region_blocks(region_cells(rz))), dim3(256), 0, s, db,
+            hipLaunchKernelGGL(fwd_pass_kernel, dim3(grid_blocks(region_cells(rz))), dim3(256), 0, s, db,
                                ry, dc, rz, n, 2, sz, 0);
             const Region pb = region_of(fwd_texels(lo[0], hi[0], sx, ni), fwd_texels(lo[1], hi[1], sy, ni),
                                         fwd_texels(lo[2], hi[2], sz, ni));
-            hipLaunchKernelGGL(fwd_pack_region_kernel, dim3(region_blocks(region_cells(pb))), dim3(256), 0, s, vox,
+            hipLaunchKernelGGL(fwd_pack_kernel, dim3(grid_blocks(region_cells(pb))), dim3(256), 0, s, vox,
                                dc, rz, dst, pb, n, sx, sy, sz);
           } else {
-            hipLaunchKernelGGL(fwd_pack_region_kernel, dim3(region_blocks(region_cells(box))), dim3(256), 0, s, vox,
+            hipLaunchKernelGGL(fwd_pack_kernel, dim3(grid_blocks(region_cells(box))), dim3(256), 0, s, vox,
                                static_cast<const uint8_t*>(nullptr), box, dst, box, n, sx, sy, sz);
           }
         }
@@ -869,37 +843,34 @@ void launch_volume_edit_passes(const uint8_t* vox, uint8_t* tmp, uint16_t* packe
     // the z pass reads y-pass values kDistCap - 1 cells to both sides in z, the y pass x-pass values in y
     const Span iy = dist_span(lo[1], hi[1], 2 * r1, ni), iz = dist_span(lo[2], hi[2], 2 * r1, ni);
     const Region rx = region_of(ax, iy, iz), ry = region_of(ax, ay, iz), rz = region_of(ax, ay, az);
-    hipLaunchKernelGGL(dist_pass_region_kernel, dim3(region_blocks(region_cells(rx))), dim3(256), 0, s, vox, whole,
+    hipLaunchKernelGGL(dist_pass_kernel, dim3(grid_blocks(region_cells(rx))), dim3(256), 0, s, vox, whole,
                        da, rx, n, 0, 1);
-    hipLaunchKernelGGL(dist_pass_region_kernel, dim3(region_blocks(region_cells(ry))), dim3(256), 0, s, da, rx, db,
+    hipLaunchKernelGGL(dist_pass_kernel, dim3(grid_blocks(region_cells(ry))), dim3(256), 0, s, da, rx, db,
                        ry, n, 1, 0);
-    hipLaunchKernelGGL(dist_pass_region_kernel, dim3(region_blocks(region_cells(rz))), dim3(256), 0, s, db, ry, da,
+    hipLaunchKernelGGL(dist_pass_kernel, dim3(grid_blocks(region_cells(rz))), dim3(256), 0, s, db, ry, da,
                        rz, n, 2, 0);
-    hipLaunchKernelGGL(pack_volume_region_kernel, dim3(region_blocks(region_cells(rz))), dim3(256), 0, s, vox, da,
+    hipLaunchKernelGGL(pack_volume_kernel, dim3(grid_blocks(region_cells(rz))), dim3(256), 0, s, vox, da,
                        rz, packed, rz, n);
   } else {
-    hipLaunchKernelGGL(pack_volume_region_kernel, dim3(region_blocks(region_cells(box))), dim3(256), 0, s, vox,
+    hipLaunchKernelGGL(pack_volume_kernel, dim3(grid_blocks(region_cells(box))), dim3(256), 0, s, vox,
                        static_cast<const uint8_t*>(nullptr), box, packed, box, n);
   }
   // texel N of an axis repeats voxel 0: rewritten when the box holds coordinate 0 of that axis
   const int wrap = (lo[0] == 0 ? 1 : 0) | (lo[1] == 0 ? 2 : 0) | (lo[2] == 0 ? 4 : 0);
   if (wrap) {
-    const uint64_t cells = uint64_t(ext[0] + (wrap & 1)) * uint64_t(ext[1] + (wrap >> 1 & 1)) *
-                           uint64_t(ext[2] + (wrap >> 2 & 1));
-    hipLaunchKernelGGL(edge_pack_region_kernel, dim3(region_blocks(cells)), dim3(256), 0, s, vox, packed, pvol,
+    const EdgeSlabs e = edge_slabs(box, wrap);
+    hipLaunchKernelGGL(edge_pack_kernel, dim3(grid_blocks(e.cz + e.cy + e.cx)), dim3(256), 0, s, vox, packed, pvol,
                        octants, box, wrap, n);
   }
 }
 
 void launch_glass_share(const uint8_t* vox, uint64_t total, unsigned long long* out, hipStream_t s) {
-  const unsigned b = unsigned(std::min<uint64_t>((total + 255) / 256, 16384));
-  hipLaunchKernelGGL(glass_share_kernel, dim3(b), dim3(256), 0, s, vox, total, out);
+  hipLaunchKernelGGL(glass_share_kernel, dim3(grid_blocks(total)), dim3(256), 0, s, vox, total, out);
 }
 
 void launch_build_scene(uint8_t* vox, int scene, uint32_t n, const float* noise, hipStream_t s) {
   const uint64_t vol = uint64_t(n) * n * n;
-  const unsigned blocks = unsigned(std::min<uint64_t>((vol + 255) / 256, 16384));
-  hipLaunchKernelGGL(build_scene_kernel, dim3(blocks), dim3(256), 0, s, vox, scene, n, noise);
+  hipLaunchKernelGGL(build_scene_kernel, dim3(grid_blocks(vol)), dim3(256), 0, s, vox, scene, n, noise);
 }
 
 void launch_assemble_blocks(const uint32_t* bands, uint64_t band_words, int32_t k, int32_t sh, int32_t width,
@@ -918,8 +889,7 @@ void launch_assemble_blocks(const uint32_t* bands, uint64_t band_words, int32_t 
 void launch_pack_rgb8(const uint32_t* rgba, uint64_t pixels, uint8_t* rgb, hipStream_t s) {
   const uint64_t quads = pixels / 4u;
   if (quads == 0) return;
-  const unsigned blocks = unsigned(std::min<uint64_t>((quads + 255) / 256, 16384));
-  hipLaunchKernelGGL(pack_rgb8_kernel, dim3(blocks), dim3(256), 0, s, reinterpret_cast<const uint4*>(rgba), quads,
+  hipLaunchKernelGGL(pack_rgb8_kernel, dim3(grid_blocks(quads)), dim3(256), 0, s, reinterpret_cast<const uint4*>(rgba), quads,
                      reinterpret_cast<uint32_t*>(rgb));
 }
 

@@ -1,11 +1,13 @@
-// vrt_edit_kernels.h — in-place voxel edits (vrt_update_volume_region): the box write with its glass
-// counts, and the region forms of the distance / forward-distance passes and packs of
-// vrt_aux_kernels.h. A region kernel works on boxes of GLOBAL voxel coordinates (origin + extent)
-// whose values live in region-local scratch (x fastest inside the box); the outside-distance terms
-// use the global coordinate, so a region pass yields exactly the full pass's bytes on its box.
+// vrt_skipfield_kernels.h — the skip field of the packed volume(s): the distance / forward-distance
+// passes, the packs and the plane-N pack, plus the box write of an in-place edit with its glass
+// counts. One kernel family builds the field for an upload and for vrt_update_volume_region: every
+// kernel works on boxes of GLOBAL voxel coordinates (origin + extent) whose values live in
+// region-local scratch (x fastest inside the box), and the outside-distance terms use the global
+// coordinate, so a pass over a box yields exactly the bytes a pass over the volume has on that box.
+// An upload is the edit of the box [0, N)^3: every box is then the whole volume.
 // Includes vrt_internal.h, vrt_math.h and vrt_walk.h (kDistCap, the packed texel layout).
-#ifndef VRT_EDIT_KERNELS_H
-#define VRT_EDIT_KERNELS_H
+#ifndef VRT_SKIPFIELD_KERNELS_H
+#define VRT_SKIPFIELD_KERNELS_H
 
 #include "vrt_internal.h"
 #include "vrt_math.h"
@@ -13,11 +15,15 @@
 
 namespace vrt {
 
-// A box of voxels: origin and extent in global coordinates (every extent >= 1, cells <= N^3 <= 2^30).
+// A box of voxels: origin and extent in global coordinates (every extent >= 1, inside [0, N)^3).
 struct Region {
   int32_t x0, y0, z0, ex, ey, ez;
 };
 
+// Cells are counted in 32 bits. The largest box is the whole volume at N = 1024 (single layout):
+// 2^30 cells. A grid-stride counter ends its loop below cells + gridDim * 256 <= 2^30 + 16384 * 256
+// = 2^30 + 2^22 < 2^32, so it cannot wrap; a region-local index is < cells. Offsets into the
+// canonical or a packed volume ((N+1)^3 texels) are formed in 64 bits.
 __host__ __device__ inline uint32_t region_cells(const Region& r) {
   return uint32_t(r.ex) * uint32_t(r.ey) * uint32_t(r.ez);
 }
@@ -50,13 +56,20 @@ __global__ void __launch_bounds__(256) edit_apply_kernel(const uint8_t* __restri
   }
 }
 
-// fwd_pass_kernel on a box: out box `ob` (region-local), input values in box `ib` (the canonical
-// volume itself for the first pass: ib = [0, N)^3). ib holds ob on the other two axes and, along
-// `axis`, ob extended kFwdCap - 1 cells ahead (clipped to the volume): the scan reads o < d <=
-// min(kFwdCap, outside distance) cells ahead, so every read is inside ib.
-__global__ void __launch_bounds__(256) fwd_pass_region_kernel(const uint8_t* __restrict__ in, Region ib,
-                                                              uint8_t* __restrict__ out, Region ob,
-                                                              uint32_t n, int axis, int sg, int first) {
+// One-sided pass of the octant forward distance along `axis` in direction sg = +-1:
+// out(v) = min(kFwdCap, distance to the outside pseudo-voxel ahead (N - c or c + 1),
+//              min over 0 <= o of max(o, in(v + sg*o*e_axis))),
+// where the first (x) pass reads in = 0 for a non-empty voxel and kFwdCap otherwise. x, then y,
+// then z: F(v) = min over non-empty / outside u in v's forward octant of max_a |u_a - v_a| (max
+// and min commute through the passes), i.e. the edge of the largest empty in-volume cube
+// anchored at v and extending along (sx, sy, sz). max(o, .) >= o, so the scan stops at o = d.
+// Out box `ob` (region-local), input values in box `ib` (the canonical volume itself for the first
+// pass: ib = [0, N)^3). ib holds ob on the other two axes and, along `axis`, ob extended
+// kFwdCap - 1 cells ahead (clipped to the volume): the scan reads o < d <= min(kFwdCap, outside
+// distance) cells ahead, so every read is inside ib.
+__global__ void __launch_bounds__(256) fwd_pass_kernel(const uint8_t* __restrict__ in, Region ib,
+                                                       uint8_t* __restrict__ out, Region ob, uint32_t n,
+                                                       int axis, int sg, int first) {
   const uint32_t total = region_cells(ob);
   const int64_t stride = axis == 0 ? 1 : (axis == 1 ? int64_t(ib.ex) : int64_t(ib.ex) * ib.ey);
   const int64_t step = sg > 0 ? stride : -stride;
@@ -76,13 +89,14 @@ __global__ void __launch_bounds__(256) fwd_pass_region_kernel(const uint8_t* __r
   }
 }
 
-// fwd_pack_kernel on the texel box `pb` of octant (sx, sy, sz)'s packed volume `dst`: voxel | G << 8
-// with G(w) = F(w - s) - 1 from the region-local F of box `fb` (0 when w - s is outside the
-// volume). fwd == nullptr: the edit changed no cell's emptiness, the texel keeps its G.
-__global__ void __launch_bounds__(256) fwd_pack_region_kernel(const uint8_t* __restrict__ vox,
-                                                              const uint8_t* __restrict__ fwd, Region fb,
-                                                              uint16_t* __restrict__ dst, Region pb,
-                                                              uint32_t n, int sx, int sy, int sz) {
+// Pack the texel box `pb` of octant (sx, sy, sz)'s padded (N+1)^3 volume `dst`: voxel | G << 8 with
+// G(w) = F(w - s) - 1 from the region-local F of box `fb` (0 when w - s is outside the volume or
+// F(w - s) = 0). pb lies in [0, N)^3; plane N is edge_pack_kernel's. fwd == nullptr: the edit
+// changed no cell's emptiness, the texel keeps its G.
+__global__ void __launch_bounds__(256) fwd_pack_kernel(const uint8_t* __restrict__ vox,
+                                                       const uint8_t* __restrict__ fwd, Region fb,
+                                                       uint16_t* __restrict__ dst, Region pb, uint32_t n,
+                                                       int sx, int sy, int sz) {
   const uint32_t total = region_cells(pb);
   const uint64_t p = uint64_t(n) + 1u;
   for (uint32_t q = blockIdx.x * 256u + threadIdx.x; q < total; q += gridDim.x * 256u) {
@@ -106,11 +120,16 @@ __global__ void __launch_bounds__(256) fwd_pack_region_kernel(const uint8_t* __r
   }
 }
 
-// dist_pass_kernel on a box: ib holds ob on the other two axes and, along `axis`, ob extended
+// Chebyshev distance field, one separable pass per axis (x, then y, then z), capped at
+// kDistCap: out(v) = min(kDistCap, distance to the boundary pseudo-voxels -1 and N on this axis,
+// min over |o| < kDistCap of max(|o|, in(v + o e_axis))), where the x pass reads in = 0 for a
+// non-empty voxel and kDistCap otherwise. The composition is the exact L-inf distance transform
+// (capped), so D(v) >= 1 guarantees an empty box of half-width D-1 around v inside the volume.
+// Boxes as in fwd_pass_kernel: ib holds ob on the other two axes and, along `axis`, ob extended
 // kDistCap - 1 cells to both sides (clipped to the volume).
-__global__ void __launch_bounds__(256) dist_pass_region_kernel(const uint8_t* __restrict__ in, Region ib,
-                                                               uint8_t* __restrict__ out, Region ob,
-                                                               uint32_t n, int axis, int first) {
+__global__ void __launch_bounds__(256) dist_pass_kernel(const uint8_t* __restrict__ in, Region ib,
+                                                        uint8_t* __restrict__ out, Region ob, uint32_t n,
+                                                        int axis, int first) {
   const uint32_t total = region_cells(ob);
   const int64_t stride = axis == 0 ? 1 : (axis == 1 ? int64_t(ib.ex) : int64_t(ib.ex) * ib.ey);
   for (uint32_t q = blockIdx.x * 256u + threadIdx.x; q < total; q += gridDim.x * 256u) {
@@ -133,12 +152,12 @@ __global__ void __launch_bounds__(256) dist_pass_region_kernel(const uint8_t* __
   }
 }
 
-// pack_volume_kernel on the texel box `pb` (single-volume layout): voxel | D << 8 from the
-// region-local D of box `db` (which holds pb). dist == nullptr: the texel keeps its D.
-__global__ void __launch_bounds__(256) pack_volume_region_kernel(const uint8_t* __restrict__ vox,
-                                                                 const uint8_t* __restrict__ dist, Region db,
-                                                                 uint16_t* __restrict__ dst, Region pb,
-                                                                 uint32_t n) {
+// Pack the texel box `pb` of the single-volume layout (N = 1024) into the padded (N+1)^3 format:
+// voxel | D << 8 from the region-local D of box `db` (which holds pb). dist == nullptr: the texel
+// keeps its D.
+__global__ void __launch_bounds__(256) pack_volume_kernel(const uint8_t* __restrict__ vox,
+                                                          const uint8_t* __restrict__ dist, Region db,
+                                                          uint16_t* __restrict__ dst, Region pb, uint32_t n) {
   const uint32_t total = region_cells(pb);
   const uint64_t p = uint64_t(n) + 1u;
   for (uint32_t q = blockIdx.x * 256u + threadIdx.x; q < total; q += gridDim.x * 256u) {
@@ -159,21 +178,38 @@ __global__ void __launch_bounds__(256) pack_volume_region_kernel(const uint8_t* 
   }
 }
 
-// The padded texels behind an edit box `b` that touches coordinate 0 on the axes of `wrap` (bit a:
-// axis a): texel N on such an axis repeats voxel 0 with distance 0, edges and corners (two or three
-// axes at N) included. Local index e_a on a wrapped axis stands for texel N; every one of the
-// `octants` packed volumes (pvol texels apart) gets the same texel.
-__global__ void __launch_bounds__(256) edge_pack_region_kernel(const uint8_t* __restrict__ vox,
-                                                               uint16_t* __restrict__ dst, uint64_t pvol,
-                                                               int octants, Region b, int wrap, uint32_t n) {
+// Plane N of the padded (N+1)^3 format repeats plane 0 (GL_REPEAT folded into the layout) with
+// distance 0 there (those texels are only read at c == N exactly). The padded texels behind a box
+// `b` that touches coordinate 0 on the axes of `wrap` (bit a: axis a): texel N on such an axis
+// repeats voxel 0, edges and corners (two or three axes at N) included. Local index e_a on a
+// wrapped axis stands for texel N; every one of the `octants` packed volumes (pvol texels apart)
+// gets the same texel. The cells are three disjoint slabs of the box extended by texel N on its
+// wrapped axes: z at N (every x, y), then y at N (z below N), then x at N (y, z below N).
+struct EdgeSlabs {
+  uint32_t wx, cz, cy, cx;  // extended x extent; cells of the z, y and x slabs (0: axis not wrapped)
+};
+__host__ __device__ inline EdgeSlabs edge_slabs(const Region& b, int wrap) {
   const uint32_t wx = uint32_t(b.ex) + (wrap & 1 ? 1u : 0u), wy = uint32_t(b.ey) + (wrap & 2 ? 1u : 0u);
-  const uint32_t wz = uint32_t(b.ez) + (wrap & 4 ? 1u : 0u);
-  const uint64_t total = uint64_t(wx) * wy * wz;
+  // at most 3 * 1025^2 cells in all
+  return EdgeSlabs{wx, wrap & 4 ? wx * wy : 0u, wrap & 2 ? wx * uint32_t(b.ez) : 0u,
+                   wrap & 1 ? uint32_t(b.ey) * uint32_t(b.ez) : 0u};
+}
+__global__ void __launch_bounds__(256) edge_pack_kernel(const uint8_t* __restrict__ vox,
+                                                        uint16_t* __restrict__ dst, uint64_t pvol,
+                                                        int octants, Region b, int wrap, uint32_t n) {
+  const EdgeSlabs e = edge_slabs(b, wrap);
+  const uint32_t total = e.cz + e.cy + e.cx;
   const uint64_t p = uint64_t(n) + 1u;
-  for (uint64_t q = uint64_t(blockIdx.x) * 256u + threadIdx.x; q < total; q += uint64_t(gridDim.x) * 256u) {
-    const uint32_t lx = uint32_t(q % wx), ly = uint32_t((q / wx) % wy), lz = uint32_t(q / (uint64_t(wx) * wy));
+  for (uint32_t q = blockIdx.x * 256u + threadIdx.x; q < total; q += gridDim.x * 256u) {
+    uint32_t lx, ly, lz;
+    if (q < e.cz) {
+      lx = q % e.wx, ly = q / e.wx, lz = uint32_t(b.ez);
+    } else if (q - e.cz < e.cy) {
+      lx = (q - e.cz) % e.wx, ly = uint32_t(b.ey), lz = (q - e.cz) / e.wx;
+    } else {
+      lx = uint32_t(b.ex), ly = (q - e.cz - e.cy) % uint32_t(b.ey), lz = (q - e.cz - e.cy) / uint32_t(b.ey);
+    }
     const bool nx = lx == uint32_t(b.ex), ny = ly == uint32_t(b.ey), nz = lz == uint32_t(b.ez);
-    if (!(nx || ny || nz)) continue;
     // a wrapped axis starts at 0, so texel N's source voxel 0 is the box's first cell on it
     const uint32_t si = nx ? 0u : uint32_t(b.x0) + lx, sj = ny ? 0u : uint32_t(b.y0) + ly;
     const uint32_t sk = nz ? 0u : uint32_t(b.z0) + lz;
@@ -186,4 +222,4 @@ __global__ void __launch_bounds__(256) edge_pack_region_kernel(const uint8_t* __
 
 }  // namespace vrt
 
-#endif  // VRT_EDIT_KERNELS_H
+#endif  // VRT_SKIPFIELD_KERNELS_H
