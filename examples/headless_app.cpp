@@ -20,6 +20,8 @@
 //     GL_TIME_ELAPSED readback (main.cpp:352-356) and reports each frame's own GPU time.
 //   - Utils::Screenshot of the last frame (key F1, :424-428) -> a binary PPM (--ppm), and the raw
 //     RGBA8 frame (--raw, row 0 = bottom) for tests
+//   - the cursor's question before an edit (--pick X,Y): which voxel, and which of its faces, is
+//     under that pixel of the last frame -> vrt_pick_pixels (no frame with hit records is rendered)
 // Build: make app (-> build/vrt_headless). Usage: build/vrt_headless --help
 #include <chrono>
 #include <cstdint>
@@ -48,6 +50,7 @@ struct Options {
   bool quiet = false, counters = false, pipelined = false, caller_stream = false;
   uint32_t device_mask = 1;  // bit i = HIP device i
   int warmup = 0;            // frames excluded from the reported mean
+  int pick_x = -1, pick_y = -1;  // --pick: pixel (x, y = frame row, 0 = bottom) picked after the last frame
 };
 
 void usage() {
@@ -56,7 +59,10 @@ void usage() {
       "             [--bounces R T] [--alpha A] [--ray-noise x] [--reflection-noise x]\n"
       "             [--refraction-noise x] [--day-night SECONDS_PER_FRAME] [--reset-at K]\n"
       "             [--atlas-raw FILE --atlas-size S --atlas-tile T] [--ppm FILE] [--raw FILE]\n"
-      "             [--device-mask M] [--counters] [--warmup K] [--pipelined [--caller-stream]] [--quiet]");
+      "             [--device-mask M] [--counters] [--warmup K] [--pipelined [--caller-stream]] [--quiet]\n"
+      "             [--pick X,Y]   after the last frame, print what pixel (X, Y) (Y = 0: bottom row) shows:\n"
+      "                            pick X Y voxel=<index> byte=<b> len=<length> face=<+|-><x|y|z> cell=<i>,<j>,<k>\n"
+      "                            (the sky: voxel=-1 byte=0 len=0 face=none cell=none)");
 }
 
 bool parse(int argc, char** argv, Options& o) {
@@ -94,6 +100,9 @@ bool parse(int argc, char** argv, Options& o) {
     else if (a == "--caller-stream") o.caller_stream = true;
     else if (a == "--device-mask") o.device_mask = uint32_t(std::strtoul(next(a.c_str()), nullptr, 0));
     else if (a == "--warmup") o.warmup = std::atoi(next("--warmup"));
+    else if (a == "--pick") {
+      if (std::sscanf(next("--pick"), "%d,%d", &o.pick_x, &o.pick_y) != 2) return false;
+    }
     else if (a == "--help" || a == "-h") return false;
     else {
       std::fprintf(stderr, "unknown option %s\n", a.c_str());
@@ -126,6 +135,24 @@ bool write_ppm(const std::string& path, const std::vector<uint8_t>& rgba, int w,
     for (int x = 0; x < w; ++x)
       std::memcpy(&img[head + (size_t(h - 1 - y) * w + x) * 3], &rgba[(size_t(y) * w + x) * 4], 3);
   return write_file(path, img.data(), img.size());
+}
+
+// --pick: the voxel and face under pixel (x, y) of a frame of (cam, p), by vrt_pick_pixels
+bool print_pick(vrt_ctx* rt, const vrt_camera& cam, const vrt_params& p, int n, int x, int y) {
+  const int32_t px[2] = {x, y};
+  vrt_ray_hit h;
+  if (vrt_pick_pixels(rt, &cam, &p, px, 1, &h) != VRT_OK) {
+    std::fprintf(stderr, "vrt_pick_pixels: %s\n", vrt_last_error(rt));
+    return false;
+  }
+  if (h.voxel_index < 0) {
+    std::printf("pick %d %d voxel=-1 byte=0 len=0 face=none cell=none\n", x, y);
+    return true;
+  }
+  const int v = h.voxel_index;
+  std::printf("pick %d %d voxel=%d byte=%u len=%.9g face=%c%c cell=%d,%d,%d\n", x, y, v, (h.face >> 8) & 0xFFu,
+              double(h.ray_length), (h.face & 4u) ? '-' : '+', "xyz"[h.face & 3u], v % n, v / n % n, v / (n * n));
+  return true;
 }
 
 }  // namespace
@@ -256,6 +283,7 @@ int main(int argc, char** argv) {
     (void)hipStreamDestroy(s);
     if (status == 0 && !o.raw.empty() && !write_file(o.raw, frame.data(), frame.size())) status = 1;
     if (status == 0 && !o.ppm.empty() && !write_ppm(o.ppm, frame, o.width, o.height)) status = 1;
+    if (status == 0 && o.pick_x >= 0 && !print_pick(rt, cam, p, o.n, o.pick_x, o.pick_y)) status = 1;
     vrt_destroy(rt);
     return status;
   }
@@ -295,6 +323,7 @@ int main(int argc, char** argv) {
                 o.counters ? " (exact instance, counting)" : "");
   if (status == 0 && !o.raw.empty() && !write_file(o.raw, frame.data(), frame.size())) status = 1;
   if (status == 0 && !o.ppm.empty() && !write_ppm(o.ppm, frame, o.width, o.height)) status = 1;
+  if (status == 0 && o.pick_x >= 0 && !print_pick(rt, cam, p, o.n, o.pick_x, o.pick_y)) status = 1;  // p: the last frame's
   vrt_destroy(rt);
   return status;
 }

@@ -226,7 +226,8 @@ int vrt_set_certified(vrt_ctx* ctx, int32_t mode);
 int vrt_certified(const vrt_ctx* ctx);
 
 /* ABI v8 (r02): device timestamps of the async band launches (vrt_render_rows*_async,
- * vrt_render_temporal_rows*_async on the first device): vrt_set_launch_timing(ctx, n) creates
+ * vrt_render_temporal_rows*_async on the first device) and of the ray-query launches (vrt_cast_rays*,
+ * vrt_pick_pixels: one launch per call): vrt_set_launch_timing(ctx, n) creates
  * timing events for the next n launches (0: off; it synchronises the first device when replacing
  * earlier events), each launch then records its kernel's start and end on the device
  * (hipExtLaunchKernelGGL); vrt_launch_timing waits for the recorded launches, returns the sum of
@@ -333,6 +334,68 @@ int vrt_render_rows_pitched_async(vrt_ctx* ctx, const vrt_camera* cam, const vrt
                                   int32_t row0, int32_t rows, int32_t row_step, int64_t pitch,
                                   float* d_out_rgba, vrt_hit* d_out_hit, uint64_t* d_counters,
                                   void* hip_stream);
+
+/* ---- ray queries (added within v15: detect by symbol lookup) -------------------------------- */
+/* Batched ray casts and pixel picks on the resident volume, without rendering a frame: which voxel,
+ * and which of its faces, a ray or the cursor meets (the question an editor asks before
+ * vrt_update_volume_region), whether a segment hits anything, whether a point sees another. One ray
+ * per GPU lane through the frame kernels' own exact walks (RayMarch / RayMarchShadow, voxel.glsl:
+ * 302-384 / :259-300), so every field below is bit-exact against the CPU oracle's march of the same
+ * ray. Queries run on the context's first device. */
+
+/* 32 bytes, 16-byte aligned in device buffers. Volume coordinates: the shader's ray.pos, i.e.
+ * world + N/2 (voxel.glsl:430); the volume is [0, N]^3. dir is used as given (RayMarch does not
+ * normalise it; ray_length is the parameter along dir, a distance when |dir| = 1). */
+typedef struct { float origin[3]; float max_length; float dir[3]; uint32_t reserved; } vrt_ray;
+
+/* 32 bytes. The first 16 bytes are a vrt_hit. */
+typedef struct {
+  int32_t voxel_index;   /* texel GetVoxel read (canonical, REPEAT wrap as vrt_hit), -1 = none */
+  float ray_length;      /* RayIntersection.rayLength, 0 if none */
+  uint32_t steps;        /* iterations of this one march */
+  uint32_t flags;        /* VRT_HIT_FLAG_TIE3 | VRT_HIT_FLAG_STEP_CAP | VRT_RAY_FLAG_BLOCKED */
+  float point[3];        /* RayIntersection.point, 0 if none */
+  uint32_t face;         /* bits 0-1: axis (intersectionAxis row, tie 3 clamped to 2); bit 2: the
+                            normal -sign(dir[axis]) is negative; bits 8-15: the voxel byte */
+} vrt_ray_hit;
+
+#define VRT_RAY_FLAG_BLOCKED 8u
+enum { VRT_CAST_NEAREST = 0, VRT_CAST_OCCLUSION = 1 };
+
+/* `count` rays from the DEVICE buffer d_rays into the DEVICE buffer d_hits (both 16-byte aligned, on
+ * the context's first device), enqueued on `hip_stream` (hipStream_t, NULL = default): no host
+ * synchronisation, no allocation. Ordering against edits and uploads on a caller stream is the
+ * caller's, as for vrt_render_rows_async.
+ *   VRT_CAST_NEAREST: RayMarch of a ray in air from ray length 0, ended at the ray's max_length (the
+ *     loop-top test `rayLength < max_length`, voxel.glsl:317, so the step that starts below it still
+ *     lands). The first non-empty voxel is the hit, glass included. A miss writes voxel_index = -1
+ *     and zeros elsewhere; steps and flags are kept.
+ *   VRT_CAST_OCCLUSION: RayMarchShadow along dir, in which glass does not block. Writes voxel_index =
+ *     -1, ray_length = 0, point = 0, face = 0; steps and the TIE3 / STEP_CAP flags come from the walk,
+ *     and VRT_RAY_FLAG_BLOCKED is set when an opaque voxel is met before max_length.
+ * Nothing on the device validates a ray: a direction with a zero, tiny (below 2^-64), huge (above
+ * 1e4) or non-finite component gets whatever the literal replay of the shader's loop produces (e.g.
+ * an all-zero direction ends after one step, NaN lengths end at once), bounded by VRT_MAX_STEPS
+ * (VRT_HIT_FLAG_STEP_CAP); every load stays inside the volume.
+ * VRT_ERR_NO_VOLUME without a resident volume; VRT_ERR_INVALID for count < 0 or > 2^30, an unknown
+ * mode, a null or not 16-byte aligned pointer with count > 0. count == 0 is a successful no-op. */
+int vrt_cast_rays_async(vrt_ctx* ctx, const vrt_ray* d_rays, int64_t count, int32_t mode,
+                        vrt_ray_hit* d_hits, void* hip_stream);
+
+/* The same from and to HOST buffers, synchronous, through context-owned device staging that grows
+ * on demand (freed by vrt_destroy). Runs on a context stream, after any preceding
+ * vrt_update_volume_region (which returns only when the edit is complete). */
+int vrt_cast_rays(vrt_ctx* ctx, const vrt_ray* rays, int64_t count, int32_t mode, vrt_ray_hit* hits);
+
+/* Pixel picks (HOST buffers, synchronous): `pixels` holds `count` pairs {px, py}, py = frame row,
+ * 0 = bottom. The kernel builds each pixel's primary ray exactly as a frame of (cam, params) does
+ * (vertex stage at the pixel centre, RandomizeDirection at params->ray_noise and params->time) and
+ * marches it in VRT_CAST_NEAREST mode with params->max_ray_length, so the first 8 bytes of a record
+ * equal the vrt_hit that vrt_render writes for that pixel; point and face are what an editor needs
+ * (the face's neighbour cell is where a placed block goes). Only those params fields are read.
+ * VRT_ERR_INVALID for a pixel outside the image, null pointers with count > 0 or count < 0. */
+int vrt_pick_pixels(vrt_ctx* ctx, const vrt_camera* cam, const vrt_params* params,
+                    const int32_t* pixels, int32_t count, vrt_ray_hit* hits);
 
 /* ---- textured mode (voxel.glsl without _COLOR_ONLY) --------------------- */
 /* With vrt_params.color_only = 0 the kernel shades with the textured material table

@@ -16,6 +16,8 @@ from . import abi
 from .abi import (  # noqa: F401  (re-exported vocabulary)
     COUNTER_NAMES,
     HIT_DTYPE,
+    RAY_DTYPE,
+    RAY_HIT_DTYPE,
     SCENE_GLASS_CUBE,
     SCENE_REFRACTION,
     SCENE_TERRAIN,
@@ -219,6 +221,53 @@ def volume_edit_plan(n: int, octants: int, origin, extent):
     return [tuple(int(v) for v in row) for row in out.reshape(-1, 6)[:k]]
 
 
+def make_rays(origins, dirs, max_length=100.0) -> np.ndarray:
+    """vrt_ray records (RAY_DTYPE) from [count, 3] origins and directions in volume coordinates (the
+    volume is [0, N]^3; directions are used as given) and a max_length, one value or one per ray."""
+    o = np.asarray(origins, np.float32).reshape(-1, 3)
+    d = np.asarray(dirs, np.float32).reshape(-1, 3)
+    if len(o) != len(d):
+        raise ValueError("make_rays: as many origins as directions")
+    rays = np.zeros(len(o), dtype=RAY_DTYPE)
+    rays["origin"] = o
+    rays["dir"] = d
+    rays["max_length"] = np.asarray(max_length, np.float32)
+    return rays
+
+
+def _cast_mode(mode) -> int:
+    """VRT_CAST_* of a mode name ("nearest", "occlusion") or number."""
+    return abi.CAST_MODES[mode] if isinstance(mode, str) else int(mode)
+
+
+def hit_normal(hits) -> np.ndarray:
+    """The hit face's outward normal per vrt_ray_hit record, int8 [count, 3]: +-1 on the face's axis
+    (bits 0-1 of `face`; bit 2: negative), zero for records without a hit."""
+    h = np.asarray(hits).reshape(-1)
+    out = np.zeros((len(h), 3), np.int8)
+    found = h["voxel_index"] >= 0
+    axis = (h["face"] & 3).astype(np.intp)
+    sign = np.where(h["face"] & 4, -1, 1).astype(np.int8)
+    rows = np.nonzero(found)[0]
+    out[rows, axis[rows]] = sign[rows]
+    return out
+
+
+def hit_cell(hits, n: int):
+    """(i, j, k) of the hit voxels (voxel_index = i + j n + k n^2), -1 on every axis without a hit."""
+    idx = np.asarray(hits).reshape(-1)["voxel_index"].astype(np.int64)
+    found = idx >= 0
+    return (np.where(found, idx % n, -1), np.where(found, idx // n % n, -1), np.where(found, idx // (n * n), -1))
+
+
+def adjacent_cell(hits, n: int):
+    """hit_cell + hit_normal: the cell in front of the hit face, where a placed block goes. It may lie
+    outside [0, n) (a face on the volume's border); -1 on every axis without a hit."""
+    nrm = hit_normal(hits).astype(np.int64)
+    i, j, k = hit_cell(hits, n)
+    return i + nrm[:, 0], j + nrm[:, 1], k + nrm[:, 2]
+
+
 def comm_unique_id() -> bytes:
     """vrt_comm_unique_id: a new RCCL unique id (rank 0 of a one-process-per-GPU job creates one
     per communicator and the job distributes them)."""
@@ -304,6 +353,34 @@ class Renderer:
         self._check(self._lib.vrt_update_volume_region_device(self._h, C.byref(o3), C.byref(e3), d_ptr or None,
                                                               stream or None),
                     "vrt_update_volume_region_device")
+
+    def cast_rays(self, rays: np.ndarray, mode="nearest") -> np.ndarray:
+        """vrt_cast_rays: `rays` (RAY_DTYPE records, e.g. make_rays()) against the resident volume,
+        synchronously; returns RAY_HIT_DTYPE records. mode "nearest": the first non-empty voxel on
+        the ray within its max_length (glass included) with hit point and face; "occlusion": only
+        whether an opaque voxel blocks it (flags & VRT_RAY_FLAG_BLOCKED; glass does not block)."""
+        r = np.ascontiguousarray(rays, dtype=RAY_DTYPE).reshape(-1)
+        hits = np.empty(len(r), dtype=RAY_HIT_DTYPE)
+        self._check(self._lib.vrt_cast_rays(self._h, r.ctypes.data, len(r), _cast_mode(mode),
+                                            hits.ctypes.data), "vrt_cast_rays")
+        return hits
+
+    def cast_rays_async(self, d_rays: int, count: int, d_hits: int, mode="nearest", stream: int = 0):
+        """vrt_cast_rays_async: `count` vrt_ray records at the device pointer d_rays into vrt_ray_hit
+        records at d_hits (both 16-byte aligned, e.g. torch tensors' data_ptr()), enqueued on a HIP
+        stream: no host synchronisation, no allocation."""
+        self._check(self._lib.vrt_cast_rays_async(self._h, d_rays or None, count, _cast_mode(mode),
+                                                  d_hits or None, stream or None), "vrt_cast_rays_async")
+
+    def pick(self, cam: Camera, params: Params, pixels) -> np.ndarray:
+        """vrt_pick_pixels: what the primary rays of `pixels` ([count, 2] of (px, py), py = 0 the
+        bottom row) of a frame of (cam, params) hit: RAY_HIT_DTYPE records whose voxel_index and
+        ray_length equal render()'s hit records at those pixels, with the hit point and face."""
+        px = np.ascontiguousarray(pixels, dtype=np.int32).reshape(-1, 2)
+        hits = np.empty(len(px), dtype=RAY_HIT_DTYPE)
+        self._check(self._lib.vrt_pick_pixels(self._h, C.byref(cam), C.byref(params), px.ctypes.data, len(px),
+                                              hits.ctypes.data), "vrt_pick_pixels")
+        return hits
 
     def debug_packed_volume(self) -> np.ndarray:
         """The kernel's device volumes [octant][z][y][x] ((N+1)^3 u16 voxel | G << 8 each; 8

@@ -93,12 +93,45 @@ class Stats(C.Structure):
 # numpy dtype of one vrt_hit record
 HIT_DTYPE = [("voxel_index", "<i4"), ("ray_length", "<f4"), ("steps", "<u4"), ("flags", "<u4")]
 
+# ray queries (vrt_cast_rays*, vrt_pick_pixels)
+VRT_RAY_FLAG_BLOCKED = 8
+VRT_CAST_NEAREST = 0
+VRT_CAST_OCCLUSION = 1
+CAST_MODES = {"nearest": VRT_CAST_NEAREST, "occlusion": VRT_CAST_OCCLUSION}
+
+
+class Ray(C.Structure):
+    _fields_ = [
+        ("origin", C.c_float * 3),
+        ("max_length", C.c_float),
+        ("dir", C.c_float * 3),
+        ("reserved", C.c_uint32),
+    ]
+
+
+class RayHit(C.Structure):
+    _fields_ = [
+        ("voxel_index", C.c_int32),
+        ("ray_length", C.c_float),
+        ("steps", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("point", C.c_float * 3),
+        ("face", C.c_uint32),
+    ]
+
+
+# numpy dtypes of one vrt_ray and one vrt_ray_hit record (the latter starts with a vrt_hit)
+RAY_DTYPE = [("origin", "<f4", (3,)), ("max_length", "<f4"), ("dir", "<f4", (3,)), ("reserved", "<u4")]
+RAY_HIT_DTYPE = HIT_DTYPE + [("point", "<f4", (3,)), ("face", "<u4")]
+
 # name -> (restype, argtypes): every function include/vrt.h declares
 # entry points added after ABI v12 (an older build loaded by VRT_LIB with VRT_LIB_ABI=<its version>
 # may lack exactly these)
 ADDED_IN = {"vrt_render_temporal_batch_async": 14, "vrt_set_cert_trees": 15,
             # added within v15 (in-place edits): a v15 build from before them lacks these three
-            "vrt_update_volume_region": 16, "vrt_update_volume_region_device": 16, "vrt_volume_edit_plan": 16}
+            "vrt_update_volume_region": 16, "vrt_update_volume_region_device": 16, "vrt_volume_edit_plan": 16,
+            # added within v15 after the edits (ray queries)
+            "vrt_cast_rays_async": 16, "vrt_cast_rays": 16, "vrt_pick_pixels": 16}
 
 SIGNATURES = {
     "vrt_abi_version": (C.c_int, []),
@@ -132,6 +165,11 @@ SIGNATURES = {
                                                   C.POINTER(C.c_int32 * 3), C.c_void_p, C.c_void_p]),
     "vrt_volume_edit_plan": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int32 * 3),
                                        C.POINTER(C.c_int32 * 3), C.c_void_p]),
+    # added within v15 (detect by symbol lookup): ray queries
+    "vrt_cast_rays_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
+    "vrt_cast_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
+    "vrt_pick_pixels": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.c_void_p, C.c_int32,
+                                  C.c_void_p]),
     "vrt_build_scene_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p]),
     "vrt_debug_packed_volume": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
     "vrt_debug_collectives": (C.c_int, [C.c_void_p]),

@@ -167,6 +167,11 @@ struct vrt_ctx {
   bool slot_valid[kRing] = {};
   void* h_stage = nullptr;              // pinned host staging of synchronous frames (k bands in)
   size_t h_stage_bytes = 0;
+  // first device: staging of the synchronous ray queries (vrt_cast_rays, vrt_pick_pixels), query_cap
+  // records of 32 bytes each; grows on demand
+  void* d_query_in = nullptr;
+  vrt_ray_hit* d_query_out = nullptr;
+  size_t query_cap = 0;
   // ABI v12: this process's rank of a one-process-per-GPU job (vrt_comm_join): one RCCL
   // communicator per lane, so that frames in flight on different lane streams gather without
   // ordering each other (a communicator's operations run in issue order)
@@ -395,6 +400,11 @@ int check_render_args(vrt_ctx* ctx, const vrt_camera* cam, const vrt_params* p) 
   return VRT_OK;
 }
 
+// KArgs::ostride: bytes from one octant's packed (N+1)^3 u16 volume to the next (0: a single volume)
+uint32_t octant_stride(const Shard& s) {
+  return s.octants == 8 ? uint32_t(uint64_t(s.n + 1) * (s.n + 1) * (s.n + 1) * sizeof(uint16_t)) : 0u;
+}
+
 vrt::KArgs make_args(const vrt_ctx* ctx, const Shard& s, const vrt_camera* cam, const vrt_params* p,
                      int32_t row0, int32_t rows, int32_t row_step) {
   vrt::KArgs a;
@@ -424,7 +434,7 @@ vrt::KArgs make_args(const vrt_ctx* ctx, const Shard& s, const vrt_camera* cam, 
   a.row_step = row_step;
   a.row_blk_sh = 0;
   a.pitch = cam->width;
-  a.ostride = s.octants == 8 ? uint32_t(uint64_t(s.n + 1) * (s.n + 1) * (s.n + 1) * sizeof(uint16_t)) : 0u;
+  a.ostride = octant_stride(s);
   a.max_refl = p->max_reflections;
   a.max_transp = p->max_transparencies;
   a.textured = p->color_only ? 0 : 1;
@@ -1222,6 +1232,8 @@ void vrt_destroy(vrt_ctx* c) {
       if (e) (void)hipEventDestroy(e);
     if (c->ev_gathered) (void)hipEventDestroy(c->ev_gathered);
     if (c->h_stage) (void)hipHostFree(c->h_stage);
+    if (c->d_query_in) (void)hipFree(c->d_query_in);
+    if (c->d_query_out) (void)hipFree(c->d_query_out);
     if (!c->lt_ev.empty()) (void)hipDeviceSynchronize();
     for (hipEvent_t e : c->lt_ev) (void)hipEventDestroy(e);
   }
@@ -1598,6 +1610,112 @@ int vrt_render_rows_async(vrt_ctx* ctx, const vrt_camera* cam, const vrt_params*
   if (!cam) return fail(ctx, VRT_ERR_INVALID, "null camera");
   return vrt_render_rows_pitched_async(ctx, cam, p, row0, rows, row_step, cam->width, d_out_rgba, d_out_hit,
                                        d_counters, hip_stream);
+}
+
+// ---- ray queries (vrt_query_kernels.h) ---------------------------------------------------------
+
+// Arguments shared by the casts. Device buffers (the kernel's 16-byte loads and stores) must be
+// 16-byte aligned; host buffers are only copied.
+static int check_cast(vrt_ctx* ctx, const void* rays, int64_t count, int32_t mode, const void* hits, bool device) {
+  if (!ctx->sh[0].d_vox_pad) return fail(ctx, VRT_ERR_NO_VOLUME, "no volume uploaded");
+  if (count < 0 || count > (int64_t(1) << 30)) return fail(ctx, VRT_ERR_INVALID, "ray count must be in [0, 2^30]");
+  if (mode != VRT_CAST_NEAREST && mode != VRT_CAST_OCCLUSION) return fail(ctx, VRT_ERR_INVALID, "unknown cast mode");
+  if (count > 0 && (!rays || !hits)) return fail(ctx, VRT_ERR_INVALID, "null ray or hit buffer");
+  if (device && count > 0 && ((reinterpret_cast<uintptr_t>(rays) | reinterpret_cast<uintptr_t>(hits)) & 15u) != 0)
+    return fail(ctx, VRT_ERR_INVALID, "device ray and hit buffers must be 16-byte aligned");
+  return VRT_OK;
+}
+
+// The argument block of a cast: ray_query_kernel reads the volume's fields only
+static vrt::KArgs cast_args(const Shard& s) {
+  vrt::KArgs a{};
+  a.n = s.n;
+  a.fn = float(s.n);
+  a.ostride = octant_stride(s);
+  return a;
+}
+
+// The synchronous queries' staging on the first device (the current one): `records` of 32 bytes in
+// and out. The queries are synchronous, so no launch still reads buffers that are replaced here.
+static int ensure_query_stage(vrt_ctx* ctx, size_t records) {
+  static_assert(sizeof(vrt_ray) == 32 && sizeof(vrt_ray_hit) == 32, "query records are 32 bytes");
+  if (ctx->query_cap >= records) return VRT_OK;
+  const size_t cap = std::max<size_t>(std::max(records, 2 * ctx->query_cap), 4096);
+  if (ctx->d_query_in) (void)hipFree(ctx->d_query_in);
+  if (ctx->d_query_out) (void)hipFree(ctx->d_query_out);
+  ctx->d_query_in = nullptr;
+  ctx->d_query_out = nullptr;
+  ctx->query_cap = 0;
+  if (hipMalloc(&ctx->d_query_in, cap * sizeof(vrt_ray)) != hipSuccess ||
+      hipMalloc(&ctx->d_query_out, cap * sizeof(vrt_ray_hit)) != hipSuccess) {
+    if (ctx->d_query_in) (void)hipFree(ctx->d_query_in);
+    ctx->d_query_in = nullptr;
+    ctx->d_query_out = nullptr;
+    return fail(ctx, VRT_ERR_OOM, "hipMalloc ray-query staging");
+  }
+  ctx->query_cap = cap;
+  return VRT_OK;
+}
+
+// `in` (host, in_bytes) to the staging, the query kernel, the records back to `hits` (host); waits
+static int run_query_staged(vrt_ctx* ctx, const vrt::KArgs& a, int32_t kind, const void* in, size_t in_bytes,
+                            size_t count, vrt_ray_hit* hits) {
+  DeviceGuard guard;
+  Shard& s = ctx->sh[0];
+  VRT_HIP(ctx, hipSetDevice(s.device));
+  const int st = ensure_query_stage(ctx, count);
+  if (st != VRT_OK) return st;
+  hipStream_t qs = main_stream(s);
+  VRT_HIP(ctx, hipMemcpyAsync(ctx->d_query_in, in, in_bytes, hipMemcpyHostToDevice, qs));
+  hipEvent_t eb, ee;
+  launch_timing_events(ctx, eb, ee);
+  vrt::launch_ray_query(a, kind, s.d_vox_pad, ctx->d_query_in, uint32_t(count), ctx->d_query_out, qs, eb, ee);
+  VRT_HIP(ctx, hipGetLastError());
+  VRT_HIP(ctx, hipMemcpyAsync(hits, ctx->d_query_out, count * sizeof(vrt_ray_hit), hipMemcpyDeviceToHost, qs));
+  VRT_HIP(ctx, hipStreamSynchronize(qs));
+  return VRT_OK;
+}
+
+int vrt_cast_rays_async(vrt_ctx* ctx, const vrt_ray* d_rays, int64_t count, int32_t mode, vrt_ray_hit* d_hits,
+                        void* hip_stream) {
+  if (!ctx) return VRT_ERR_INVALID;
+  const int st = check_cast(ctx, d_rays, count, mode, d_hits, true);
+  if (st != VRT_OK || count == 0) return st;
+  Shard& s = ctx->sh[0];
+  hipEvent_t eb, ee;
+  launch_timing_events(ctx, eb, ee);
+  vrt::launch_ray_query(cast_args(s), mode, s.d_vox_pad, d_rays, uint32_t(count), d_hits,
+                        static_cast<hipStream_t>(hip_stream), eb, ee);
+  VRT_HIP(ctx, hipGetLastError());
+  return VRT_OK;
+}
+
+int vrt_cast_rays(vrt_ctx* ctx, const vrt_ray* rays, int64_t count, int32_t mode, vrt_ray_hit* hits) {
+  if (!ctx) return VRT_ERR_INVALID;
+  const int st = check_cast(ctx, rays, count, mode, hits, false);
+  if (st != VRT_OK || count == 0) return st;
+  return run_query_staged(ctx, cast_args(ctx->sh[0]), mode, rays, size_t(count) * sizeof(vrt_ray), size_t(count),
+                          hits);
+}
+
+int vrt_pick_pixels(vrt_ctx* ctx, const vrt_camera* cam, const vrt_params* p, const int32_t* pixels, int32_t count,
+                    vrt_ray_hit* hits) {
+  if (!ctx) return VRT_ERR_INVALID;
+  if (!cam || !p) return fail(ctx, VRT_ERR_INVALID, "null camera or params");
+  Shard& s = ctx->sh[0];
+  if (!s.d_vox_pad) return fail(ctx, VRT_ERR_NO_VOLUME, "no volume uploaded");
+  if (cam->width <= 0 || cam->height <= 0 || cam->width > 32768 || cam->height > 32768)
+    return fail(ctx, VRT_ERR_INVALID, "bad image size");
+  if (count < 0) return fail(ctx, VRT_ERR_INVALID, "pixel count must be >= 0");
+  if (count == 0) return VRT_OK;
+  if (!pixels || !hits) return fail(ctx, VRT_ERR_INVALID, "null pixel or hit buffer");
+  for (int32_t i = 0; i < count; ++i)
+    if (pixels[2 * i] < 0 || pixels[2 * i] >= cam->width || pixels[2 * i + 1] < 0 || pixels[2 * i + 1] >= cam->height)
+      return fail(ctx, VRT_ERR_INVALID, "pixel outside the image");
+  // the frame's argument block, as the frame launches fill it (launch): primary_ray reads it
+  vrt::KArgs a = make_args(ctx, s, cam, p, 0, cam->height, 1);
+  a.vdiv_ok = vertex_div_ranges_ok(a.inv_pv) ? 1u : 0u;
+  return run_query_staged(ctx, a, vrt::kQueryPick, pixels, size_t(count) * 2 * sizeof(int32_t), size_t(count), hits);
 }
 
 int vrt_render_temporal_blocks_pitched_async(vrt_ctx* ctx, const vrt_camera* cam, const vrt_params* p,

@@ -106,6 +106,13 @@ constexpr uint32_t kDeferDense = 32;        // deferred pixels from which a wave
 void launch_render(const KArgs& a, bool stats, const uint16_t* vox, float4* out, vrt_hit* hit,
                    unsigned long long* cnt_rep, hipStream_t s, hipEvent_t ev_begin = nullptr,
                    hipEvent_t ev_end = nullptr);
+// ray_query_kernel (vrt_query_kernels.h): `count` (>= 1) queries, one per lane, into hits. kind =
+// VRT_CAST_NEAREST / VRT_CAST_OCCLUSION: `in` holds vrt_ray records and only a.n, a.fn and a.ostride are
+// read; kQueryPick: `in` holds {px, py} pairs and `a` is the frame's argument block (make_args).
+// ev_begin / ev_end: optional device timestamps, as launch_render's
+constexpr int32_t kQueryPick = 2;
+void launch_ray_query(const KArgs& a, int32_t kind, const uint16_t* vox, const void* in, uint32_t count,
+                      vrt_ray_hit* hits, hipStream_t s, hipEvent_t ev_begin = nullptr, hipEvent_t ev_end = nullptr);
 // fold the counter replicas into dst (accumulating) and re-zero them
 void launch_reduce_counters(unsigned long long* rep, unsigned long long* dst, hipStream_t s);
 // in-place edit of the box [lo, lo + ext) (vrt_update_volume_region), inside [0, N)^3:

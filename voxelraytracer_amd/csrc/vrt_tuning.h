@@ -12,7 +12,7 @@
      defined(VRT_FAT_WAVES) || defined(VRT_SPARSE_BATCH) || defined(VRT_SPARSE_BATCH_TEX) ||                    \
      defined(VRT_SPARSE_BATCH_FAT) || defined(VRT_EXACT_PRIO) || defined(VRT_FWD_CAP) || defined(VRT_WG_WAVES) || \
      defined(VRT_ORD_DIV) || defined(VRT_ORD_MIN_ROUNDS) || defined(VRT_DEFER_GRID_DIV) ||                      \
-     defined(VRT_DEFER_GRID_DIV_COLOR)) &&                                                                      \
+     defined(VRT_DEFER_GRID_DIV_COLOR) || defined(VRT_QUERY_WG_WAVES)) &&                                      \
     !defined(VRT_DIAGNOSTIC_BUILD)
 #error "the VRT_* tuning values are A/B knobs of make variant builds (make variant NAME=... DEFS=-DVRT_...=...)"
 #endif
@@ -61,6 +61,9 @@
 #endif
 #ifndef VRT_DEFER_GRID_DIV_COLOR
 #define VRT_DEFER_GRID_DIV_COLOR VRT_DEFER_GRID_DIV
+#endif
+#ifndef VRT_QUERY_WG_WAVES
+#define VRT_QUERY_WG_WAVES 1
 #endif
 
 namespace vrt {
@@ -119,6 +122,13 @@ constexpr uint32_t kOrdMinRounds = VRT_ORD_MIN_ROUNDS;
 // C3 0.0843 -> 0.0713 ms against 32; 4 no better; profiles/r03_s11, r03_s12)
 constexpr uint32_t kDeferGridDiv = VRT_DEFER_GRID_DIV;
 constexpr uint32_t kDeferGridDivColor = VRT_DEFER_GRID_DIV_COLOR;  // the same for colour-only frames
+
+// waves per workgroup of the ray-query kernel (vrt_query_kernels.h). One: a wave lasts as long as its
+// longest ray and shares nothing with its neighbours (no barrier, a 3 KB axis table of its own), so a
+// one-wave workgroup returns its slot the moment that ray ends, as in the exact pass. No larger value
+// has been measured.
+constexpr int kQueryWgWaves = VRT_QUERY_WG_WAVES;
+static_assert(kQueryWgWaves >= 1 && kQueryWgWaves <= 4, "1 to 4 waves per query workgroup");
 
 }  // namespace vrt
 
