@@ -23,7 +23,9 @@
  *     frame of a glass-heavy volume or of >= 8 rounds of resident waves: one deferred launch, see
  *     vrt_set_exact_pass); a device-output frame at u_Alpha = 1
  *     is one launch, and up to four frames are in flight (ABI v9). The *_async band entry points
- *     run on the context's first (root) device.
+ *     run on the context's first (root) device, as do the ray queries (vrt_cast_rays*,
+ *     vrt_pick_pixels: which voxel a ray meets) and the shaded ray queries (vrt_trace_rays*,
+ *     vrt_trace_pixels: which colour a ray sees).
  */
 #ifndef VRT_H
 #define VRT_H
@@ -227,7 +229,7 @@ int vrt_certified(const vrt_ctx* ctx);
 
 /* ABI v8 (r02): device timestamps of the async band launches (vrt_render_rows*_async,
  * vrt_render_temporal_rows*_async on the first device) and of the ray-query launches (vrt_cast_rays*,
- * vrt_pick_pixels: one launch per call): vrt_set_launch_timing(ctx, n) creates
+ * vrt_pick_pixels, vrt_trace_rays*, vrt_trace_pixels: one launch per call): vrt_set_launch_timing(ctx, n) creates
  * timing events for the next n launches (0: off; it synchronises the first device when replacing
  * earlier events), each launch then records its kernel's start and end on the device
  * (hipExtLaunchKernelGGL); vrt_launch_timing waits for the recorded launches, returns the sum of
@@ -396,6 +398,62 @@ int vrt_cast_rays(vrt_ctx* ctx, const vrt_ray* rays, int64_t count, int32_t mode
  * VRT_ERR_INVALID for a pixel outside the image, null pointers with count > 0 or count < 0. */
 int vrt_pick_pixels(vrt_ctx* ctx, const vrt_camera* cam, const vrt_params* params,
                     const int32_t* pixels, int32_t count, vrt_ray_hit* hits);
+
+/* ---- shaded ray queries (added within v15: detect by symbol lookup) -------------------------- */
+/* What a ray SEES: fragment main (voxel.glsl:425-452) for a list of rays or of pixels, without a
+ * frame: other camera models (panorama, cube map, orthographic, stereo, lens jitter, supersampling;
+ * vrt.panorama_rays of the Python host is a worked example), re-shading a sparse set of pixels after
+ * an edit, the colour along an arbitrary world ray. One ray tree per GPU lane through the frame
+ * kernels' own exact path (TraceWithShadow, the bounce stack, the colour folded in the reference's
+ * order) with exact walks only, never certified walks: a record is the shader's for every input,
+ * hit fields bit-exact and colour within the frame's tolerance against the CPU oracle. Traces run on
+ * the context's first device. */
+
+/* 32 bytes. The first 16 bytes are a vrt_hit of the ray's tree, as vrt_render writes per pixel. */
+typedef struct {
+  int32_t voxel_index;  /* the FIRST march's hit texel, -1 = none */
+  float ray_length;     /* its RayIntersection.rayLength, 0 if none */
+  uint32_t steps;       /* DDA + shadow-DDA iterations of the whole tree */
+  uint32_t flags;       /* VRT_HIT_FLAG_TIE3 | STEP_CAP | STACK_FULL */
+  float rgba[4];        /* f_Color: the folded colour, a = 1 (voxel.glsl:451) */
+} vrt_ray_color;
+
+/* `count` rays from the DEVICE buffer d_rays into the DEVICE buffer d_out (both 16-byte aligned, on
+ * the context's first device), enqueued on `hip_stream` (hipStream_t, NULL = default): no host
+ * synchronisation, no allocation, capturable like vrt_cast_rays_async; one launch per call. Ordering
+ * against edits and uploads on a caller stream is the caller's.
+ * Each ray runs main with stack[0] = Ray(origin, dir, 0, 1.0, air, 0, 0):
+ *   - origin and dir are in volume coordinates (vrt_ray) and used as given: no RandomizeDirection on
+ *     the first ray, so params->ray_noise is not read, and dir is not normalised, as in vrt_cast_rays;
+ *   - the ray's own max_length plays u_MaxRayLength for the whole tree: secondary rays inherit the
+ *     accumulated length and shadow rays get what is left, exactly as in a frame;
+ *     params->max_ray_length is not read;
+ *   - sun_dir, time, reflection_noise and refraction_noise, max_reflections and max_transparencies,
+ *     color_only and the atlas fields are the frame's; textured mode (color_only = 0) uses the
+ *     context's atlas by the render calls' rule (vrt_upload_atlas).
+ * Nothing on the device validates a ray: a direction with a zero, tiny (below 2^-64), huge (above
+ * 1e4) or non-finite component gets whatever the literal replay of the shader's loops produces,
+ * bounded by VRT_MAX_STEPS per march (VRT_HIT_FLAG_STEP_CAP); every load stays inside the volume.
+ * VRT_ERR_NO_VOLUME without a resident volume; VRT_ERR_INVALID for count < 0 or > 2^30, null params,
+ * a null or not 16-byte aligned pointer with count > 0, max_reflections or max_transparencies outside
+ * 0..8, and textured mode without a matching atlas (the render calls' rule). count == 0 is a
+ * successful no-op. A failed call writes nothing. */
+int vrt_trace_rays_async(vrt_ctx* ctx, const vrt_ray* d_rays, int64_t count, const vrt_params* params,
+                         vrt_ray_color* d_out, void* hip_stream);
+
+/* The same from and to HOST buffers, synchronous, through the ray queries' device staging (records are
+ * 32 bytes either way). Runs on a context stream, after any preceding vrt_update_volume_region. */
+int vrt_trace_rays(vrt_ctx* ctx, const vrt_ray* rays, int64_t count, const vrt_params* params,
+                   vrt_ray_color* out);
+
+/* Shaded pixels (HOST buffers, synchronous): `pixels` holds `count` pairs {px, py}, py = frame row,
+ * 0 = bottom. The kernel builds each pixel's primary ray exactly as a frame of (cam, params) does
+ * (vertex stage at the pixel centre, RandomizeDirection at params->ray_noise and params->time) and
+ * traces it with params->max_ray_length: the record's first 16 bytes equal the vrt_hit that
+ * vrt_render writes for that pixel, and rgba equals its float colour, bit for bit.
+ * VRT_ERR_INVALID also for a null camera, a bad image size or a pixel outside the image. */
+int vrt_trace_pixels(vrt_ctx* ctx, const vrt_camera* cam, const vrt_params* params,
+                     const int32_t* pixels, int32_t count, vrt_ray_color* out);
 
 /* ---- textured mode (voxel.glsl without _COLOR_ONLY) --------------------- */
 /* With vrt_params.color_only = 0 the kernel shades with the textured material table

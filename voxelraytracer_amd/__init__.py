@@ -16,6 +16,7 @@ from . import abi
 from .abi import (  # noqa: F401  (re-exported vocabulary)
     COUNTER_NAMES,
     HIT_DTYPE,
+    RAY_COLOR_DTYPE,
     RAY_DTYPE,
     RAY_HIT_DTYPE,
     SCENE_GLASS_CUBE,
@@ -235,6 +236,27 @@ def make_rays(origins, dirs, max_length=100.0) -> np.ndarray:
     return rays
 
 
+def panorama_rays(width: int, height: int, pos, n: int, max_length=100.0) -> np.ndarray:
+    """The ray list of an equirectangular panorama seen from the world position `pos` in a volume of
+    size n, as RAY_DTYPE records of shape [height, width] for Renderer.trace_rays: a camera model the
+    pinhole frame (inv_pv) cannot express. Row 0 is the bottom row. Column i looks along the longitude
+    lon = 2 pi (i + 0.5) / width - pi and row j along the latitude lat = pi (j + 0.5) / height - pi / 2,
+    direction (sin(lon) cos(lat), sin(lat), -cos(lon) cos(lat)): the image's centre looks along -z (the
+    pinhole camera's view at zero rotation; for an odd width it is column (width - 1) / 2 exactly),
+    longitude grows with the column towards +x, the left and right edges meet at +z, and the bottom and
+    top rows are half a row from -y and +y. Directions have unit length in float32; every origin is
+    pos + n / 2 (volume coordinates, voxel.glsl:430)."""
+    lon = 2.0 * np.pi * (np.arange(width, dtype=np.float64) + 0.5) / width - np.pi
+    lat = np.pi * (np.arange(height, dtype=np.float64) + 0.5) / height - 0.5 * np.pi
+    d = np.empty((height, width, 3), np.float64)
+    d[..., 0] = np.cos(lat)[:, None] * np.sin(lon)[None, :]
+    d[..., 1] = np.sin(lat)[:, None]
+    d[..., 2] = -np.cos(lat)[:, None] * np.cos(lon)[None, :]
+    origin = np.asarray(pos, np.float32).reshape(3) + np.float32(n) * np.float32(0.5)
+    rays = make_rays(np.broadcast_to(origin, (height * width, 3)), d.reshape(-1, 3), max_length)
+    return rays.reshape(height, width)
+
+
 def _cast_mode(mode) -> int:
     """VRT_CAST_* of a mode name ("nearest", "occlusion") or number."""
     return abi.CAST_MODES[mode] if isinstance(mode, str) else int(mode)
@@ -381,6 +403,35 @@ class Renderer:
         self._check(self._lib.vrt_pick_pixels(self._h, C.byref(cam), C.byref(params), px.ctypes.data, len(px),
                                               hits.ctypes.data), "vrt_pick_pixels")
         return hits
+
+    def trace_rays(self, rays: np.ndarray, params: Params) -> np.ndarray:
+        """vrt_trace_rays: what each of `rays` (RAY_DTYPE records, e.g. make_rays() or panorama_rays())
+        sees, synchronously: the shader's whole ray tree (shadow rays, reflections, refractions) from the
+        ray as given, with the ray's own max_length as u_MaxRayLength and the rest of `params` as in a
+        frame (ray_noise and max_ray_length are not read). Returns RAY_COLOR_DTYPE records in the shape of
+        `rays`: the first march's hit, the tree's steps and flags, and the colour rgba (a = 1)."""
+        r = np.ascontiguousarray(rays, dtype=RAY_DTYPE)
+        out = np.empty(r.shape, dtype=RAY_COLOR_DTYPE)
+        self._check(self._lib.vrt_trace_rays(self._h, r.ctypes.data, r.size, C.byref(params), out.ctypes.data),
+                    "vrt_trace_rays")
+        return out
+
+    def trace_rays_async(self, d_rays: int, count: int, params: Params, d_out: int, stream: int = 0):
+        """vrt_trace_rays_async: `count` vrt_ray records at the device pointer d_rays into vrt_ray_color
+        records at d_out (both 16-byte aligned, e.g. torch tensors' data_ptr()), enqueued on a HIP
+        stream: no host synchronisation, no allocation."""
+        self._check(self._lib.vrt_trace_rays_async(self._h, d_rays or None, count, C.byref(params), d_out or None,
+                                                   stream or None), "vrt_trace_rays_async")
+
+    def trace_pixels(self, cam: Camera, params: Params, pixels) -> np.ndarray:
+        """vrt_trace_pixels: the pixels `pixels` ([count, 2] of (px, py), py = 0 the bottom row) of a
+        frame of (cam, params), without rendering it: RAY_COLOR_DTYPE records whose first four fields
+        equal render()'s hit records at those pixels and whose rgba equals its float frame, bit for bit."""
+        px = np.ascontiguousarray(pixels, dtype=np.int32).reshape(-1, 2)
+        out = np.empty(len(px), dtype=RAY_COLOR_DTYPE)
+        self._check(self._lib.vrt_trace_pixels(self._h, C.byref(cam), C.byref(params), px.ctypes.data, len(px),
+                                               out.ctypes.data), "vrt_trace_pixels")
+        return out
 
     def debug_packed_volume(self) -> np.ndarray:
         """The kernel's device volumes [octant][z][y][x] ((N+1)^3 u16 voxel | G << 8 each; 8

@@ -124,6 +124,21 @@ class RayHit(C.Structure):
 RAY_DTYPE = [("origin", "<f4", (3,)), ("max_length", "<f4"), ("dir", "<f4", (3,)), ("reserved", "<u4")]
 RAY_HIT_DTYPE = HIT_DTYPE + [("point", "<f4", (3,)), ("face", "<u4")]
 
+
+# shaded ray queries (vrt_trace_rays*, vrt_trace_pixels)
+class RayColor(C.Structure):
+    _fields_ = [
+        ("voxel_index", C.c_int32),
+        ("ray_length", C.c_float),
+        ("steps", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("rgba", C.c_float * 4),
+    ]
+
+
+# numpy dtype of one vrt_ray_color record (it starts with a vrt_hit)
+RAY_COLOR_DTYPE = HIT_DTYPE + [("rgba", "<f4", (4,))]
+
 # name -> (restype, argtypes): every function include/vrt.h declares
 # entry points added after ABI v12 (an older build loaded by VRT_LIB with VRT_LIB_ABI=<its version>
 # may lack exactly these)
@@ -131,7 +146,9 @@ ADDED_IN = {"vrt_render_temporal_batch_async": 14, "vrt_set_cert_trees": 15,
             # added within v15 (in-place edits): a v15 build from before them lacks these three
             "vrt_update_volume_region": 16, "vrt_update_volume_region_device": 16, "vrt_volume_edit_plan": 16,
             # added within v15 after the edits (ray queries)
-            "vrt_cast_rays_async": 16, "vrt_cast_rays": 16, "vrt_pick_pixels": 16}
+            "vrt_cast_rays_async": 16, "vrt_cast_rays": 16, "vrt_pick_pixels": 16,
+            # added within v15 after the ray queries (shaded ray queries)
+            "vrt_trace_rays_async": 16, "vrt_trace_rays": 16, "vrt_trace_pixels": 16}
 
 SIGNATURES = {
     "vrt_abi_version": (C.c_int, []),
@@ -170,6 +187,12 @@ SIGNATURES = {
     "vrt_cast_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
     "vrt_pick_pixels": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.c_void_p, C.c_int32,
                                   C.c_void_p]),
+    # added within v15 (detect by symbol lookup): shaded ray queries
+    "vrt_trace_rays_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(Params), C.c_void_p,
+                                       C.c_void_p]),
+    "vrt_trace_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(Params), C.c_void_p]),
+    "vrt_trace_pixels": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.c_void_p, C.c_int32,
+                                   C.c_void_p]),
     "vrt_build_scene_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p]),
     "vrt_debug_packed_volume": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
     "vrt_debug_collectives": (C.c_int, [C.c_void_p]),

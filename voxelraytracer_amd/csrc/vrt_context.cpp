@@ -167,8 +167,8 @@ struct vrt_ctx {
   bool slot_valid[kRing] = {};
   void* h_stage = nullptr;              // pinned host staging of synchronous frames (k bands in)
   size_t h_stage_bytes = 0;
-  // first device: staging of the synchronous ray queries (vrt_cast_rays, vrt_pick_pixels), query_cap
-  // records of 32 bytes each; grows on demand
+  // first device: staging of the synchronous ray queries (vrt_cast_rays, vrt_pick_pixels, vrt_trace_rays,
+  // vrt_trace_pixels), query_cap records of 32 bytes each; grows on demand
   void* d_query_in = nullptr;
   vrt_ray_hit* d_query_out = nullptr;
   size_t query_cap = 0;
@@ -1657,9 +1657,11 @@ static int ensure_query_stage(vrt_ctx* ctx, size_t records) {
   return VRT_OK;
 }
 
-// `in` (host, in_bytes) to the staging, the query kernel, the records back to `hits` (host); waits
-static int run_query_staged(vrt_ctx* ctx, const vrt::KArgs& a, int32_t kind, const void* in, size_t in_bytes,
-                            size_t count, vrt_ray_hit* hits) {
+// `in` (host, in_bytes) to the staging, one query launch over `count` queries (shaded: launch_ray_trace
+// of kind kTraceRays / kTracePixels, else launch_ray_query), the 32-byte records back to `out` (host); waits
+static int run_query_staged(vrt_ctx* ctx, const vrt::KArgs& a, int32_t kind, bool shaded, const void* in,
+                            size_t in_bytes, size_t count, void* out) {
+  static_assert(sizeof(vrt_ray_color) == sizeof(vrt_ray_hit), "one staging for both record types");
   DeviceGuard guard;
   Shard& s = ctx->sh[0];
   VRT_HIP(ctx, hipSetDevice(s.device));
@@ -1669,9 +1671,13 @@ static int run_query_staged(vrt_ctx* ctx, const vrt::KArgs& a, int32_t kind, con
   VRT_HIP(ctx, hipMemcpyAsync(ctx->d_query_in, in, in_bytes, hipMemcpyHostToDevice, qs));
   hipEvent_t eb, ee;
   launch_timing_events(ctx, eb, ee);
-  vrt::launch_ray_query(a, kind, s.d_vox_pad, ctx->d_query_in, uint32_t(count), ctx->d_query_out, qs, eb, ee);
+  if (shaded)
+    vrt::launch_ray_trace(a, kind, s.d_vox_pad, ctx->d_query_in, uint32_t(count),
+                          reinterpret_cast<vrt_ray_color*>(ctx->d_query_out), qs, eb, ee);
+  else
+    vrt::launch_ray_query(a, kind, s.d_vox_pad, ctx->d_query_in, uint32_t(count), ctx->d_query_out, qs, eb, ee);
   VRT_HIP(ctx, hipGetLastError());
-  VRT_HIP(ctx, hipMemcpyAsync(hits, ctx->d_query_out, count * sizeof(vrt_ray_hit), hipMemcpyDeviceToHost, qs));
+  VRT_HIP(ctx, hipMemcpyAsync(out, ctx->d_query_out, count * sizeof(vrt_ray_hit), hipMemcpyDeviceToHost, qs));
   VRT_HIP(ctx, hipStreamSynchronize(qs));
   return VRT_OK;
 }
@@ -1694,8 +1700,8 @@ int vrt_cast_rays(vrt_ctx* ctx, const vrt_ray* rays, int64_t count, int32_t mode
   if (!ctx) return VRT_ERR_INVALID;
   const int st = check_cast(ctx, rays, count, mode, hits, false);
   if (st != VRT_OK || count == 0) return st;
-  return run_query_staged(ctx, cast_args(ctx->sh[0]), mode, rays, size_t(count) * sizeof(vrt_ray), size_t(count),
-                          hits);
+  return run_query_staged(ctx, cast_args(ctx->sh[0]), mode, false, rays, size_t(count) * sizeof(vrt_ray),
+                          size_t(count), hits);
 }
 
 int vrt_pick_pixels(vrt_ctx* ctx, const vrt_camera* cam, const vrt_params* p, const int32_t* pixels, int32_t count,
@@ -1715,7 +1721,89 @@ int vrt_pick_pixels(vrt_ctx* ctx, const vrt_camera* cam, const vrt_params* p, co
   // the frame's argument block, as the frame launches fill it (launch): primary_ray reads it
   vrt::KArgs a = make_args(ctx, s, cam, p, 0, cam->height, 1);
   a.vdiv_ok = vertex_div_ranges_ok(a.inv_pv) ? 1u : 0u;
-  return run_query_staged(ctx, a, vrt::kQueryPick, pixels, size_t(count) * 2 * sizeof(int32_t), size_t(count), hits);
+  return run_query_staged(ctx, a, vrt::kQueryPick, false, pixels, size_t(count) * 2 * sizeof(int32_t), size_t(count),
+                          hits);
+}
+
+// ---- shaded ray queries (vrt_trace_kernels.h) --------------------------------------------------
+
+// The params of a trace call: max_reflections and max_transparencies in vrt_params' range 0..8 each (so
+// the stack fits kMaxStack), as VRT_ERR_INVALID, then what the render calls check (check_render_args: the
+// atlas rules, which upload a changed atlas as the render calls do). Last of a call's checks: a call that
+// fails another check uploads nothing.
+static int check_trace_params(vrt_ctx* ctx, const vrt_camera* cam, const vrt_params* p) {
+  constexpr int32_t kMaxDepth = (vrt::kMaxStack - 1) / 2;
+  if (p->max_reflections < 0 || p->max_transparencies < 0 || p->max_reflections > kMaxDepth ||
+      p->max_transparencies > kMaxDepth)
+    return fail(ctx, VRT_ERR_INVALID, "max_reflections and max_transparencies must be in [0, 8]");
+  return check_render_args(ctx, cam, p);
+}
+
+// Arguments shared by vrt_trace_rays*. Device buffers (the kernel's 16-byte loads and stores) must be
+// 16-byte aligned; host buffers are only copied.
+static int check_trace_rays(vrt_ctx* ctx, const void* rays, int64_t count, const vrt_params* p, const void* out,
+                            bool device, const vrt_camera* dummy) {
+  if (!p) return fail(ctx, VRT_ERR_INVALID, "null params");
+  if (!ctx->sh[0].d_vox_pad) return fail(ctx, VRT_ERR_NO_VOLUME, "no volume uploaded");
+  if (count < 0 || count > (int64_t(1) << 30)) return fail(ctx, VRT_ERR_INVALID, "ray count must be in [0, 2^30]");
+  if (count > 0 && (!rays || !out)) return fail(ctx, VRT_ERR_INVALID, "null ray or output buffer");
+  if (device && count > 0 && ((reinterpret_cast<uintptr_t>(rays) | reinterpret_cast<uintptr_t>(out)) & 15u) != 0)
+    return fail(ctx, VRT_ERR_INVALID, "device ray and output buffers must be 16-byte aligned");
+  return check_trace_params(ctx, dummy, p);
+}
+
+// The rays form needs no camera: a 1 x 1 image whose matrix no lane reads
+static vrt_camera trace_dummy_camera() {
+  vrt_camera cam{};
+  cam.width = cam.height = 1;
+  return cam;
+}
+
+int vrt_trace_rays_async(vrt_ctx* ctx, const vrt_ray* d_rays, int64_t count, const vrt_params* p,
+                         vrt_ray_color* d_out, void* hip_stream) {
+  if (!ctx) return VRT_ERR_INVALID;
+  const vrt_camera cam = trace_dummy_camera();
+  const int st = check_trace_rays(ctx, d_rays, count, p, d_out, true, &cam);
+  if (st != VRT_OK || count == 0) return st;
+  Shard& s = ctx->sh[0];
+  hipEvent_t eb, ee;
+  launch_timing_events(ctx, eb, ee);
+  vrt::launch_ray_trace(make_args(ctx, s, &cam, p, 0, 1, 1), vrt::kTraceRays, s.d_vox_pad, d_rays, uint32_t(count),
+                        d_out, static_cast<hipStream_t>(hip_stream), eb, ee);
+  VRT_HIP(ctx, hipGetLastError());
+  return VRT_OK;
+}
+
+int vrt_trace_rays(vrt_ctx* ctx, const vrt_ray* rays, int64_t count, const vrt_params* p, vrt_ray_color* out) {
+  if (!ctx) return VRT_ERR_INVALID;
+  const vrt_camera cam = trace_dummy_camera();
+  const int st = check_trace_rays(ctx, rays, count, p, out, false, &cam);
+  if (st != VRT_OK || count == 0) return st;
+  Shard& s = ctx->sh[0];
+  return run_query_staged(ctx, make_args(ctx, s, &cam, p, 0, 1, 1), vrt::kTraceRays, true, rays,
+                          size_t(count) * sizeof(vrt_ray), size_t(count), out);
+}
+
+int vrt_trace_pixels(vrt_ctx* ctx, const vrt_camera* cam, const vrt_params* p, const int32_t* pixels, int32_t count,
+                     vrt_ray_color* out) {
+  if (!ctx) return VRT_ERR_INVALID;
+  if (!cam || !p) return fail(ctx, VRT_ERR_INVALID, "null camera or params");
+  Shard& s = ctx->sh[0];
+  if (!s.d_vox_pad) return fail(ctx, VRT_ERR_NO_VOLUME, "no volume uploaded");
+  if (cam->width <= 0 || cam->height <= 0 || cam->width > 32768 || cam->height > 32768)
+    return fail(ctx, VRT_ERR_INVALID, "bad image size");
+  if (count < 0) return fail(ctx, VRT_ERR_INVALID, "pixel count must be >= 0");
+  if (count > 0 && (!pixels || !out)) return fail(ctx, VRT_ERR_INVALID, "null pixel or output buffer");
+  for (int32_t i = 0; i < count; ++i)
+    if (pixels[2 * i] < 0 || pixels[2 * i] >= cam->width || pixels[2 * i + 1] < 0 || pixels[2 * i + 1] >= cam->height)
+      return fail(ctx, VRT_ERR_INVALID, "pixel outside the image");
+  const int st = check_trace_params(ctx, cam, p);
+  if (st != VRT_OK || count == 0) return st;
+  // the frame's argument block, as the frame launches fill it (launch): primary_ray reads it
+  vrt::KArgs a = make_args(ctx, s, cam, p, 0, cam->height, 1);
+  a.vdiv_ok = vertex_div_ranges_ok(a.inv_pv) ? 1u : 0u;
+  return run_query_staged(ctx, a, vrt::kTracePixels, true, pixels, size_t(count) * 2 * sizeof(int32_t),
+                          size_t(count), out);
 }
 
 int vrt_render_temporal_blocks_pitched_async(vrt_ctx* ctx, const vrt_camera* cam, const vrt_params* p,

@@ -113,6 +113,14 @@ void launch_render(const KArgs& a, bool stats, const uint16_t* vox, float4* out,
 constexpr int32_t kQueryPick = 2;
 void launch_ray_query(const KArgs& a, int32_t kind, const uint16_t* vox, const void* in, uint32_t count,
                       vrt_ray_hit* hits, hipStream_t s, hipEvent_t ev_begin = nullptr, hipEvent_t ev_end = nullptr);
+// ray_trace_kernel (vrt_trace_kernels.h): `count` (>= 1) shaded queries, one per lane, into `out`; the
+// instance is chosen from (kind, a.textured). `a` is a frame's argument block (make_args) with the caller's
+// params. kTraceRays: `in` holds vrt_ray records, each with its own max_length (a.max_len, a.ray_noise and
+// the camera fields are not read); kTracePixels: `in` holds {px, py} pairs of the frame `a` describes.
+// ev_begin / ev_end: optional device timestamps, as launch_render's
+constexpr int32_t kTraceRays = 0, kTracePixels = 1;
+void launch_ray_trace(const KArgs& a, int32_t kind, const uint16_t* vox, const void* in, uint32_t count,
+                      vrt_ray_color* out, hipStream_t s, hipEvent_t ev_begin = nullptr, hipEvent_t ev_end = nullptr);
 // fold the counter replicas into dst (accumulating) and re-zero them
 void launch_reduce_counters(unsigned long long* rep, unsigned long long* dst, hipStream_t s);
 // in-place edit of the box [lo, lo + ext) (vrt_update_volume_region), inside [0, N)^3:

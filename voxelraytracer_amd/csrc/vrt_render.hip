@@ -2,8 +2,9 @@
 // C-ABI context around them is vrt_context.cpp (include/vrt.h). One translation unit: this file
 // holds the pixel epilogue, the tile order, the primary ray, the bounce-stack exact_pixel, the two
 // frame kernels and the host launch wrappers; the rest is in the headers included below, in
-// dependency order (vrt_tuning.h through vrt_internal.h), and in vrt_query_kernels.h (the ray-query
-// kernel, included after the primary ray it calls).
+// dependency order (vrt_tuning.h through vrt_internal.h), and in vrt_query_kernels.h and
+// vrt_trace_kernels.h (the ray-query and shaded ray-query kernels, included after the primary ray and
+// exact_pixel they call).
 //
 // One work-item per pixel; a 128-thread workgroup covers a 16x8 pixel tile and each wave64 an
 // 8x8 sub-tile, so the 64 rays of a wave start coherent. Every float operation of the DDA is
@@ -667,12 +668,14 @@ __global__ void __launch_bounds__(64, WAVES) exact_pass_kernel(KArgs a, const ui
 
 // the ray-query kernel (vrt_cast_rays*, vrt_pick_pixels): here because it calls init_ctx and primary_ray
 #include "vrt_query_kernels.h"
+// the shaded ray-query kernels (vrt_trace_rays*, vrt_trace_pixels): after exact_pixel, which they call
+#include "vrt_trace_kernels.h"
 
 namespace vrt {
 
 // ------------------------------------------------------------------------------- launches --
-// Host wrappers of the kernels above, of vrt_aux_kernels.h, vrt_skipfield_kernels.h and
-// vrt_query_kernels.h (vrt_internal.h); the C-ABI context is vrt_context.cpp.
+// Host wrappers of the kernels above, of vrt_aux_kernels.h, vrt_skipfield_kernels.h,
+// vrt_query_kernels.h and vrt_trace_kernels.h (vrt_internal.h); the C-ABI context is vrt_context.cpp.
 
 // workgroups of 256 for a grid-stride loop over `items`
 static unsigned grid_blocks(uint64_t items) { return unsigned(std::min<uint64_t>((items + 255) / 256, 16384)); }
@@ -750,6 +753,20 @@ void launch_ray_query(const KArgs& a, int32_t kind, const uint16_t* vox, const v
                           reinterpret_cast<uint4*>(hits));
   else
     hipLaunchKernelGGL(kern, grid, dim3(kQueryWg), 0, s, a, vox, in, count, reinterpret_cast<uint4*>(hits));
+}
+
+void launch_ray_trace(const KArgs& a, int32_t kind, const uint16_t* vox, const void* in, uint32_t count,
+                      vrt_ray_color* out, hipStream_t s, hipEvent_t ev_begin, hipEvent_t ev_end) {
+  auto kern = kind == kTracePixels
+                  ? (a.textured ? ray_trace_kernel<kTracePixels, true> : ray_trace_kernel<kTracePixels, false>)
+                  : (a.textured ? ray_trace_kernel<kTraceRays, true> : ray_trace_kernel<kTraceRays, false>);
+  // one lane per query: ceil(count / kTraceWg) workgroups (count <= 2^30)
+  const dim3 grid((count + uint32_t(kTraceWg) - 1u) / uint32_t(kTraceWg));
+  if (ev_begin || ev_end)
+    hipExtLaunchKernelGGL(kern, grid, dim3(kTraceWg), 0, s, ev_begin, ev_end, 0, a, vox, in, count,
+                          reinterpret_cast<uint4*>(out));
+  else
+    hipLaunchKernelGGL(kern, grid, dim3(kTraceWg), 0, s, a, vox, in, count, reinterpret_cast<uint4*>(out));
 }
 
 void launch_reduce_counters(unsigned long long* rep, unsigned long long* dst, hipStream_t s) {

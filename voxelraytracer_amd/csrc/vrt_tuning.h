@@ -12,7 +12,8 @@
      defined(VRT_FAT_WAVES) || defined(VRT_SPARSE_BATCH) || defined(VRT_SPARSE_BATCH_TEX) ||                    \
      defined(VRT_SPARSE_BATCH_FAT) || defined(VRT_EXACT_PRIO) || defined(VRT_FWD_CAP) || defined(VRT_WG_WAVES) || \
      defined(VRT_ORD_DIV) || defined(VRT_ORD_MIN_ROUNDS) || defined(VRT_DEFER_GRID_DIV) ||                      \
-     defined(VRT_DEFER_GRID_DIV_COLOR) || defined(VRT_QUERY_WG_WAVES)) &&                                      \
+     defined(VRT_DEFER_GRID_DIV_COLOR) || defined(VRT_QUERY_WG_WAVES) || defined(VRT_TRACE_WG_WAVES) ||         \
+     defined(VRT_TRACE_MIN_WAVES)) &&                                                                         \
     !defined(VRT_DIAGNOSTIC_BUILD)
 #error "the VRT_* tuning values are A/B knobs of make variant builds (make variant NAME=... DEFS=-DVRT_...=...)"
 #endif
@@ -64,6 +65,12 @@
 #endif
 #ifndef VRT_QUERY_WG_WAVES
 #define VRT_QUERY_WG_WAVES 1
+#endif
+#ifndef VRT_TRACE_WG_WAVES
+#define VRT_TRACE_WG_WAVES 1
+#endif
+#ifndef VRT_TRACE_MIN_WAVES
+#define VRT_TRACE_MIN_WAVES 6
 #endif
 
 namespace vrt {
@@ -129,6 +136,18 @@ constexpr uint32_t kDeferGridDivColor = VRT_DEFER_GRID_DIV_COLOR;  // the same f
 // has been measured.
 constexpr int kQueryWgWaves = VRT_QUERY_WG_WAVES;
 static_assert(kQueryWgWaves >= 1 && kQueryWgWaves <= 4, "1 to 4 waves per query workgroup");
+// the same for the shaded ray-query kernel (vrt_trace_kernels.h), where the reasoning holds more strongly:
+// a wave lasts as long as its longest bounce tree. Its LDS (the axis table and the bounce stack's bottom
+// entry: 5.25 KB per wave) does not bound occupancy at one wave. Two: the coherent arms within 1.4 % either
+// way, scattered rays 1.4-2.1 % slower (profiles/ray_trace_ab.txt).
+constexpr int kTraceWgWaves = VRT_TRACE_WG_WAVES;
+static_assert(kTraceWgWaves >= 1 && kTraceWgWaves <= 4, "1 to 4 waves per trace workgroup");
+// resident waves per SIMD the shaded ray-query kernel is built for. Without a promise (1) the four
+// instances take 87-93 VGPRs: 5 waves, no spills. 6 -> 80 VGPRs with at most one spilled VGPR, and every
+// pixel of the 1920x1080 benchmark camera in tile order 0.2578 -> 0.2478 ms at C3, 0.3896 -> 0.3673 at C1,
+// 2 M scattered rays 5.90 -> 5.47 and 5.75 -> 5.36 ms; 7 (72 VGPRs, 1-21 spilled) is no faster: 0.2505,
+// 0.3678, 5.45, 5.32 (profiles/ray_trace_ab.txt; the frame's STATS instance runs at 7 with 24-40 spilled)
+constexpr int kTraceMinWaves = VRT_TRACE_MIN_WAVES;
 
 }  // namespace vrt
 
