@@ -78,6 +78,15 @@ __device__ __forceinline__ uint32_t cross_texel(const Ctx& c, int i, int j, int 
   return t;
 }
 __device__ __forceinline__ bool cross_outside(uint32_t tex) { return tex >= kTexOutside; }
+// path_texel without its branch, for a walk's start (the diagonal neighbour of a cell in the volume:
+// any of its indices may be -1 or N): an outside cell loads texel 0 of the octant volume, as in
+// cross_texel, and reads 0. The load is issued at once, not behind a lane mask.
+__device__ __forceinline__ uint32_t start_texel(const Ctx& c, int i, int j, int k, uint32_t obase) {
+  const bool outside = max(max(uint32_t(i), uint32_t(j)), uint32_t(k)) >= uint32_t(c.n);
+  const uint32_t idx = mad24(mad24(uint32_t(k), c.p, uint32_t(j)), c.p, uint32_t(i));
+  const uint32_t t = load_u16_at(c.vox, outside ? 0u : idx, obase);
+  return outside ? 0u : t;
+}
 // byte of a cell the exact walk might sample at a near-edge crossing (plane N: GL_REPEAT copy)
 __device__ __forceinline__ uint32_t alt_byte(const Ctx& c, int i, int j, int k, uint32_t obase) {
   const uint32_t n = uint32_t(c.n);
@@ -100,11 +109,42 @@ __device__ __forceinline__ bool cert_event(uint32_t b, uint32_t medium) {
 // cell's box need not cover a cell behind it: it is read from the diagonal neighbour's texel,
 // G(v + s) = F(v) - 1, i.e. the box [v, v + G s].
 // LEAN: the certified pass's walks (render_kernel's DEFER instances, which run without scratch):
-// the same walk with the landing texel loaded unguarded, the crossing's texel without a branch and
-// the planes after a jump from the floored floats; every value it computes is the guarded form's,
-// bit for bit. The other instances keep the guarded forms: they sit at their register limit, and
-// the lean forms moved their scratch use up.
-template <bool SHADOW, bool LEAN = false>
+// the same walk with the start's and the landing's texel loaded unguarded, the crossing's texel
+// without a branch and the planes after a jump from the floored floats; texels, cells and planes
+// are the guarded form's, bit for bit. The other instances keep the guarded forms: they sit at
+// their register limit, and the lean forms moved their scratch use up.
+// ED false: the caller's ed is zero (a primary ray, a ray from an exact origin) and is not added.
+//
+// The bound is evaluated factored by what depends on the axis, gam_b(u) = A(u) + |1/d_b| B(u) +
+// ed_b, and the jump test as min_b(sig_b + (fg1 - B) |1/d_b| - ed_b) - A without a test of G; the
+// landing coordinate is one fma. gam, the jump parameter uj and the landing coordinate are therefore
+// not the values of the per-axis form gam_b = (q2 u + q1_b) u + q0_b (a few 2^-24 relative apart:
+// tests/test_cert_bound_forms.py), and the walk is sound by the argument, not by equality:
+//  - every term of the bound is non-negative (|d|_1, len0b, e0, ed_b, N, |1/d_b| and u = max(s1, 0)
+//    are), so A, B and gam_b are sums and products of non-negative floats: no cancellation, each of
+//    the at most six roundings on a path changes the value by at most 2^-24 relative, and the float
+//    gam_b is within a few 2^-24 relative of the real polynomial. That polynomial carries a factor 2
+//    on every 2^-24 term and the 4e-5 constant: a few 2^-24 of the k24 part is nothing against its
+//    half, and a few 2^-24 of the rest (<= 4e-5 + e0 + ed_b < 1.3e-2: under 5e-9) nothing against
+//    half the k24 part (>= 2^-24 (3N + 11 + 18 / |d|_1) > 3e-6). The float value stays above the
+//    bound with 2^-24 for k24;
+//  - (fg1 - B) |1/d_b|: fg1 - B rounds by at most 2^-24 max(G, B), which moves the product by
+//    2^-24 G |1/d_b| (<= 8e-6 |1/d_b|: G <= 128) or by 2^-24 of B |1/d_b| (inside the factor 2 as
+//    above); the fma rounds once at magnitude <= |sig_b| + G |1/d_b|, the subtractions of ed_b and
+//    A once each at no more: a few ulps of ~2000 |1/d_b| at most (N = 1024), 4e-4 |1/d_b|, the
+//    margin's margin argument made for l_b below, or 2^-24 relative of A where A dominates (the
+//    factor 2 again). The jump parameter stays below min_b(l_b - gam_b) evaluated exactly with
+//    half of kCertMargin and the bound with 2^-24 for k24 (the CPU test asserts exactly that);
+//  - the landing coordinate fma(uj, |d_b|, Ps_b) has one rounding (<= 2^-14 cell at |x| <= 2^10 +
+//    2) where the product and sum had two: the landing load's argument holds a fortiori;
+//  - G < 2 (G = 0: a cell without a box or outside the volume; G = 1, also the start texel's + 1
+//    over such a cell): fg1 = G - 65/64 <= -1/64 exactly, B >= 0, so fg1 - B rounds to a negative
+//    float; sig_b plus a negative product rounds to at most sig_b (rounding is monotone, sig_b a
+//    float); subtracting ed_b >= 0, taking the minimum (<= s1) and subtracting A >= 0 keep it at most
+//    s1: `uj > s1` is false, as the test `G >= 2` decided before. An infinite or NaN A or B (never
+//    at fast-path directions) fails the compare too: no jump.
+// The two lattice cameras of DESIGN.md §10 (certified trees) are not touched by this.
+template <bool SHADOW, bool LEAN = false, bool ED = true>
 __device__ __forceinline__ CertResult cert_walk(const Ctx& c, const f3 P, const f3 D, const f3 rcp, const float U,
                                 int cx, int cy, int cz, const float e0, const f3 ed,
                                 const float len0b, const uint32_t medium, const uint32_t tex0 = ~0u) {
@@ -125,15 +165,15 @@ __device__ __forceinline__ CertResult cert_walk(const Ctx& c, const f3 P, const 
   //   K(u) = u |d|_1 + 3 non-zero exact steps, sum_k len_k <= (K + 3)^2 / (2 |d|_1) + K (len0 + 1),
   //   gam_b(u) = 2^-24 (sum len + 2 (u + len0) + (K + 3N + 8) |1/d_b|) + 4e-5 + e0 + ed_b,
   //   gL(u) = 2^-23 sum len + 1e-4 + e0 (the length test)
+  // Factored by what depends on the axis: gam_b(u) = A(u) + |1/d_b| B(u) + ed_b,
+  //   A(u) = (q2 u + a1) u + c0, B(u) = b1 u + b0: five scalars per walk, three fma per iteration
   constexpr float k24 = 2.0f * 0x1p-24f;
   const float q2 = 0.5f * k24 * l1;
   // 18 / |d|_1 only bounds a sum: the hardware reciprocal (<= 1 ulp) scaled up by 2^-19 stays above it
   const float lin = 6.0f + l1 * (len0b + 1.0f),
               con = (18.0f * 1.0000020f) * __builtin_amdgcn_rcpf(l1) + 3.0f * (len0b + 1.0f);
-  const float nterm = 3.0f * c.fn + 11.0f;
-  const f3 q1 = mk(k24 * (lin + 2.0f + ar.x * l1), k24 * (lin + 2.0f + ar.y * l1), k24 * (lin + 2.0f + ar.z * l1));
+  const float a1 = k24 * (lin + 2.0f), b1 = k24 * l1, b0 = k24 * (3.0f * c.fn + 11.0f);
   const float c0 = k24 * (con + 2.0f * len0b) + 4e-5f + e0;
-  const f3 q0 = mk(c0 + k24 * ar.x * nterm + ed.x, c0 + k24 * ar.y * nterm + ed.y, c0 + k24 * ar.z * nterm + ed.z);
   const float g2 = 2.0f * q2, g1 = 2.0f * k24 * lin, g0 = 2.0f * k24 * con + 1e-4f + e0;
   // sign-folded start and direction: Ps_b + u |d_b| = s_b (P_b + u d_b) exactly (negation is exact),
   // so a landing cell is floor(s x) ^ m, m = 0 or ~0 (ceil(x) - 1 = ~floor(-x)), without branches
@@ -144,39 +184,52 @@ __device__ __forceinline__ CertResult cert_walk(const Ctx& c, const f3 P, const 
               (float(cz + uz) - P.z) * rcp.z);
   // start: the unguarded box from the diagonal neighbour (G(v + s) + 1 in the guarded formula)
   // (tex0: that texel, loaded by the caller beside an earlier load; ~0u: load it here)
-  uint32_t tex = (tex0 != ~0u ? tex0 : path_texel(c, cx + sx, cy + sy, cz + sz, obase)) + (1u << kDistShift);
+  uint32_t tex = (tex0 != ~0u ? tex0
+                              : (LEAN ? start_texel(c, cx + sx, cy + sy, cz + sz, obase)
+                                      : path_texel(c, cx + sx, cy + sy, cz + sz, obase))) +
+                 (1u << kDistShift);
   CTRACE(c, 100 + int(SHADOW), cx, cy, cz, P.x, P.y, P.z, U);
   CTRACE(c, 101, D.x, D.y, D.z, e0, ed.x, ed.y, ed.z);
   CERT_DIAG_ONLY(r.iters = 0;)
   for (int guard = 0; guard < kCertMaxIter; ++guard) {
     CERT_DIAG_ONLY(r.iters = guard + 1;)
     const float s1 = __builtin_fminf(sig.x, __builtin_fminf(sig.y, sig.z));
-    const int a = sig.x == s1 ? 0 : (sig.y == s1 ? 1 : 2);
     const float uu = gmax(s1, 0.0f);
-    const f3 gam = mk(__builtin_fmaf(__builtin_fmaf(q2, uu, q1.x), uu, q0.x),
-                      __builtin_fmaf(__builtin_fmaf(q2, uu, q1.y), uu, q0.y),
-                      __builtin_fmaf(__builtin_fmaf(q2, uu, q1.z), uu, q0.z));
+    const float A = __builtin_fmaf(__builtin_fmaf(q2, uu, a1), uu, c0);
+    const float B = __builtin_fmaf(b1, uu, b0);
+    // gam_b(uu), formed where a crossing needs it (ED false: the caller's ed is zero, and x + 0.0f
+    // would not fold)
+    auto gam_of = [&](float arb, float edb) {
+      const float g = __builtin_fmaf(B, arb, A);
+      return ED ? g + edb : g;
+    };
     // empty-space jump: the box [v - s, v + (G - 1) s] of this cell is empty and in the volume
-    // (only for rays in air: empty cells are events in a glass medium)
+    // (only for rays in air: empty cells are events in a glass medium). No test of G: without a
+    // box (G < 2) fg1 - B is negative and the jump parameter below is at most s1 (see above).
     const uint32_t G = tex >> kDistShift;
-    if (G >= 2u && (SHADOW || medium == 0u)) {
+    bool jumped = false;
+    if (SHADOW || medium == 0u) {
       // the box's far face on axis b is G - 1 - margin cells beyond the plane of sig_b: its
       // parameter sig_b + (G - 1 - margin) |1/d_b| up to a few ulps, far inside the margin's
       // margin |1/d_b| (|sig_b| <= ~400 |1/d_b| in a 256^3 volume: 1e-4 |1/d_b| at 3 ulps)
       const float fg1 = float(G) - (1.0f + kCertMargin);
-      const float lx = __builtin_fmaf(fg1, ar.x, sig.x);
-      const float ly = __builtin_fmaf(fg1, ar.y, sig.y);
-      const float lz = __builtin_fmaf(fg1, ar.z, sig.z);
       // per axis: the exact walk crosses the box face of axis b within gam_b of l_b, so its steps
       // up to min_b (l_b - gam_b) sample box cells (a common max(gam) would let one nearly
-      // parallel axis, |1/d_b| huge, stop every jump: ~90 us cell-by-cell walks at C3)
-      const float uj = __builtin_fminf(__builtin_fminf(lx - gam.x, ly - gam.y),
-                                       __builtin_fminf(lz - gam.z, U + 2.0f));
-      CTRACE(c, 102, G, s1, uj, gam.x, gam.y, gam.z, 0);
+      // parallel axis, |1/d_b| huge, stop every jump: ~90 us cell-by-cell walks at C3).
+      // l_b - gam_b = sig_b + (fg1 - B) |1/d_b| - ed_b - A: the axis' part in one fma, A after the minimum
+      const float fb = fg1 - B;
+      const float jx = __builtin_fmaf(fb, ar.x, sig.x), jy = __builtin_fmaf(fb, ar.y, sig.y),
+                  jz = __builtin_fmaf(fb, ar.z, sig.z);
+      const float jm = ED ? __builtin_fminf(jx - ed.x, __builtin_fminf(jy - ed.y, jz - ed.z))
+                          : __builtin_fminf(jx, __builtin_fminf(jy, jz));
+      const float uj = __builtin_fminf(jm - A, U + 2.0f);
+      CTRACE(c, 102, G, s1, uj, gam_of(ar.x, ed.x), gam_of(ar.y, ed.y), gam_of(ar.z, ed.z), 0);
       if (uj > s1) {
         // the cell the exact walk is in there: floor(x) moving up, ceil(x) - 1 moving down
-        const float fx = __builtin_floorf(Ps.x + uj * Da.x), fy = __builtin_floorf(Ps.y + uj * Da.y),
-                    fz = __builtin_floorf(Ps.z + uj * Da.z);
+        // (one rounding per coordinate: fma)
+        const float fx = __builtin_floorf(__builtin_fmaf(uj, Da.x, Ps.x)),
+                    fy = __builtin_floorf(__builtin_fmaf(uj, Da.y, Ps.y)),
+                    fz = __builtin_floorf(__builtin_fmaf(uj, Da.z, Ps.z));
         cx = int(fx) ^ mx;
         cy = int(fy) ^ my;
         cz = int(fz) ^ mz;
@@ -197,15 +250,21 @@ __device__ __forceinline__ CertResult cert_walk(const Ctx& c, const f3 P, const 
         // loaded without path_texel's bounds test: on every axis the sign-folded landing coordinate
         // is at most that of the plane of sig_b plus G - 1 - kCertMargin cells (uj <= l_b - gam_b,
         // gam_b >= 0), the box's far face pulled in by 1/64 cell, against a float error of the
-        // coordinate below 2^-16 cell (|x| <= N + 2 <= 2^10 + 2, two roundings); and it is at or
+        // coordinate of at most 2^-14 cell (|x| <= N + 2 <= 2^10 + 2, the fma's one rounding); and it is at or
         // ahead of P_b (uj > s1 >= 0, the callers' precondition above), which the box [v - s, v + (G - 1) s] (at the start: [v, v +
         // G s] from the cell of P itself) covers. Every cell of the box is in [0, N)^3 (skip_walk's
         // B(v), vrt_walk.h).
         tex = LEAN ? cell_texel(c, cx, cy, cz, obase) : path_texel(c, cx, cy, cz, obase);
-        continue;
+        jumped = true;
       }
     }
+    // (the crossing reads sig after the jump's merge, and the axis from it: the planes then live in
+    // one set of registers across the iteration; with `continue` in the jump two of them were
+    // copied out and back in every iteration)
+    if (jumped) continue;
+    const int a = sig.x == s1 ? 0 : (sig.y == s1 ? 1 : 2);
     // one crossing, s1 on axis a; prev = the crossing before it (the exact walk's len there)
+    const f3 gam = mk(gam_of(ar.x, ed.x), gam_of(ar.y, ed.y), gam_of(ar.z, ed.z));
     const f3 back = mk(sig.x - ar.x, sig.y - ar.y, sig.z - ar.z);
     const float mback = gmax(back.x, gmax(back.y, back.z));
     const float prev = gmax(mback, 0.0f);
@@ -788,8 +847,8 @@ __device__ __forceinline__ int cert_shadow_exact(const Ctx& c, const Hit& h) {
   int cx, cy, cz;
   if (!fast_path_ok(S) || !exact_start_cell(c, h.point, S, cx, cy, cz)) return -1;
   if (!start_layers_clear<true>(c, h.point, S, cx, cy, cz, 0u)) return -1;
-  const CertResult s = cert_walk<true>(c, h.point, S, c.sun_rcp, c.max_len - h.len, cx, cy, cz, 0.0f,
-                                       mk(0.0f, 0.0f, 0.0f), h.len, 0u);
+  const CertResult s = cert_walk<true, false, false>(c, h.point, S, c.sun_rcp, c.max_len - h.len, cx, cy, cz,
+                                                     0.0f, mk(0.0f, 0.0f, 0.0f), h.len, 0u);
   return s.res == CERT_UNSURE ? -1 : (s.res == CERT_HIT ? 1 : 0);
 }
 
@@ -1017,8 +1076,8 @@ __device__ __forceinline__ bool cert_pixel(const Ctx& c, const Ray& ray0, f3& co
   }
   // hardware reciprocals (<= 1 ulp): the certified walk only needs its own error bounded
   const f3 rcp = mk(__builtin_amdgcn_rcpf(D.x), __builtin_amdgcn_rcpf(D.y), __builtin_amdgcn_rcpf(D.z));
-  CertResult h = cert_walk<false, LEAN>(c, P, D, rcp, c.max_len - ray0.len, cx, cy, cz, 0.0f,
-                                        mk(0.0f, 0.0f, 0.0f), 0.0f, 0u);
+  CertResult h = cert_walk<false, LEAN, false>(c, P, D, rcp, c.max_len - ray0.len, cx, cy, cz, 0.0f,
+                                               mk(0.0f, 0.0f, 0.0f), 0.0f, 0u);
   if (us_out) *us_out = h.us;
   CERT_DIAG_ONLY(cert_diag_iters(10, h.iters);)
   if (h.res == CERT_UNSURE) { CERT_DIAG(1); return false; }

@@ -89,6 +89,11 @@ constexpr int kMinWaves = VRT_MIN_WAVES;
 // The certified pass without the exact path (render_kernel's DEFER instances) fits 64 VGPRs (8
 // waves per SIMD) with 8 bytes of scratch, but runs faster at 7 (72 VGPRs, no spills): C3 0.0464 ->
 // 0.0447, C4 0.1751 -> 0.1605, textured C3 -4 % (profiles/r03_s11, r03_s12); 6 is slower again.
+// Re-tested at 65 VGPRs (r08, the factored bound): at 8 waves the DEFER instances still need 2
+// spilled VGPRs, 8 bytes of scratch and 74-140 SGPR spills against 16-58, and run slower,
+// alternating with the 7-wave library, ms per frame 7 -> 8: C3 0.0346 / 0.0346 / 0.0348 -> 0.0358 /
+// 0.0362 / 0.0358, C2 0.0530 / 0.0529 -> 0.0550 / 0.0548, C4 0.1210 / 0.1209 -> 0.1300 / 0.1305, C1
+// 0.1207 / 0.1205 -> 0.1204 / 0.1205 (profiles/r08_walk/ab_bench.txt). 7 stays.
 constexpr int kDeferWaves = VRT_DEFER_WAVES;
 // resident waves per SIMD of the exact pass's whole-frame instance (see exact_pass_kernel, WAVES)
 constexpr int kExactWaves = VRT_EXACT_WAVES;
