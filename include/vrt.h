@@ -24,8 +24,9 @@
  *     vrt_set_exact_pass); a device-output frame at u_Alpha = 1
  *     is one launch, and up to four frames are in flight (ABI v9). The *_async band entry points
  *     run on the context's first (root) device, as do the ray queries (vrt_cast_rays*,
- *     vrt_pick_pixels: which voxel a ray meets) and the shaded ray queries (vrt_trace_rays*,
- *     vrt_trace_pixels: which colour a ray sees).
+ *     vrt_pick_pixels: which voxel a ray meets), the shaded ray queries (vrt_trace_rays*,
+ *     vrt_trace_pixels: which colour a ray sees) and the ID and depth pass (vrt_render_ids*: which
+ *     voxel and face every pixel shows, and how far away).
  */
 #ifndef VRT_H
 #define VRT_H
@@ -229,7 +230,8 @@ int vrt_certified(const vrt_ctx* ctx);
 
 /* ABI v8 (r02): device timestamps of the async band launches (vrt_render_rows*_async,
  * vrt_render_temporal_rows*_async on the first device) and of the ray-query launches (vrt_cast_rays*,
- * vrt_pick_pixels, vrt_trace_rays*, vrt_trace_pixels: one launch per call): vrt_set_launch_timing(ctx, n) creates
+ * vrt_pick_pixels, vrt_trace_rays*, vrt_trace_pixels, vrt_render_ids*: one launch per call):
+ * vrt_set_launch_timing(ctx, n) creates
  * timing events for the next n launches (0: off; it synchronises the first device when replacing
  * earlier events), each launch then records its kernel's start and end on the device
  * (hipExtLaunchKernelGGL); vrt_launch_timing waits for the recorded launches, returns the sum of
@@ -454,6 +456,58 @@ int vrt_trace_rays(vrt_ctx* ctx, const vrt_ray* rays, int64_t count, const vrt_p
  * VRT_ERR_INVALID also for a null camera, a bad image size or a pixel outside the image. */
 int vrt_trace_pixels(vrt_ctx* ctx, const vrt_camera* cam, const vrt_params* params,
                      const int32_t* pixels, int32_t count, vrt_ray_color* out);
+
+/* ---- ID and depth pass (added within v15: detect by symbol lookup) --------------------------- */
+/* What the frame SHOWS, per pixel and without shading: the voxel and the face the pixel's primary ray
+ * meets, and the hit's depth. An ID buffer outlines a selection, an edited box or the voxels under the
+ * cursor without a pick per pixel; a depth buffer composites rasterised gizmos, particles or UI against
+ * the ray-traced frame; face and voxel byte per pixel guide an edge-aware filter. Every pixel is walked by
+ * the pick's exact march, an 8x8 tile per wave, in one kernel launch: the price of vrt_pick_pixels over
+ * every pixel without its pixel list, its 32-byte records and its host staging (DESIGN.md §6 "ID and depth
+ * pass"; a certified-walk kernel for octant layouts is not part of the library yet). The pass runs on the
+ * context's first device. */
+
+/* 8 bytes. voxel_index and face are vrt_ray_hit's fields of the same names for the pixel's primary ray
+ * (a miss: voxel_index = -1, face = 0). */
+typedef struct { int32_t voxel_index; uint32_t face; } vrt_pixel_id;
+
+/* Rows [row0, row0 + rows) of the frame of (cam, params), pixel (px, row0 + i) at d_ids[i * pitch + px]
+ * (and d_depth likewise; d_depth may be NULL). DEVICE buffers on the context's first device, enqueued on
+ * hip_stream (hipStream_t, NULL = default), no host synchronisation.
+ * The primary ray is the frame's own (vertex stage at the pixel centre, RandomizeDirection at
+ * params->ray_noise and params->time), marched in VRT_CAST_NEAREST mode with params->max_ray_length:
+ * voxel_index and face equal vrt_pick_pixels' record of the pixel bit for bit, glass included. Only the
+ * params fields the pick reads are read.
+ * depth: with a the face's axis (face & 3) and `plane` the integer coordinate of the hit face along a,
+ * depth = (float(plane) - pos[a]) / dir[a] in float32 (one subtraction, one correctly rounded division),
+ * +INFINITY for a miss. It is the parameter along the NORMALISED primary direction from pos, the pixel's
+ * point on the near plane in volume coordinates (world + N/2), i.e. the Euclidean distance from that
+ * point to the hit, not from the eye and not a projected z. A caller that composites against a rasteriser
+ * converts it: the hit point is pos + depth * dir with pos and dir from the camera's inverse matrix as the
+ * vertex stage forms them (pos = near-plane point of the pixel centre, dir = normalize(far - near)); the
+ * distance from the eye adds |pos - eye| (the near-plane distance over the cosine of the pixel's angle to
+ * the view axis), and view-space z is (distance from the eye) times that cosine. depth is defined by the
+ * face's plane; it is NOT the shader's accumulated rayLength (vrt_ray_hit::ray_length), from which it
+ * differs by that sum's rounding.
+ * One call is one kernel launch (one launch for vrt_set_launch_timing): no allocation, no memset, no
+ * context-owned state, so calls on different streams do not disturb each other and a call is capturable in
+ * a hipGraph like vrt_render_rows_async.
+ * VRT_ERR_NO_VOLUME without a resident volume; VRT_ERR_INVALID for a null cam, params or d_ids, a bad image
+ * size, rows < 0 or a band outside the image, pitch < width, d_ids not 8-byte or d_depth not 4-byte
+ * aligned. rows == 0 is a successful no-op. A failed call writes nothing. */
+int vrt_render_ids_async(vrt_ctx* ctx, const vrt_camera* cam, const vrt_params* params, int32_t row0,
+                         int32_t rows, int32_t pitch, vrt_pixel_id* d_ids, float* d_depth, void* hip_stream);
+
+/* Whole frame to HOST buffers (width * height records, row 0 = bottom; depth may be NULL), synchronous,
+ * through context-owned device staging that grows on demand. Runs on a context stream, after any
+ * preceding vrt_update_volume_region. */
+int vrt_render_ids(vrt_ctx* ctx, const vrt_camera* cam, const vrt_params* params, vrt_pixel_id* ids,
+                   float* depth);
+
+/* Of the last synchronous vrt_render_ids: pixels rendered, and how many of them took the exact kernel:
+ * all of them, on every layout, while the library has no certified ID kernel. Zeros before the first such
+ * call. */
+int vrt_ids_deferred(vrt_ctx* ctx, uint64_t* pixels, uint64_t* deferred);
 
 /* ---- textured mode (voxel.glsl without _COLOR_ONLY) --------------------- */
 /* With vrt_params.color_only = 0 the kernel shades with the textured material table

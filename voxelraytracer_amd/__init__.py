@@ -16,6 +16,7 @@ from . import abi
 from .abi import (  # noqa: F401  (re-exported vocabulary)
     COUNTER_NAMES,
     HIT_DTYPE,
+    PIXEL_ID_DTYPE,
     RAY_COLOR_DTYPE,
     RAY_DTYPE,
     RAY_HIT_DTYPE,
@@ -25,6 +26,7 @@ from .abi import (  # noqa: F401  (re-exported vocabulary)
     SCENES,
     Camera,
     Params,
+    PixelId,
     VrtError,
 )
 
@@ -432,6 +434,35 @@ class Renderer:
         self._check(self._lib.vrt_trace_pixels(self._h, C.byref(cam), C.byref(params), px.ctypes.data, len(px),
                                                out.ctypes.data), "vrt_trace_pixels")
         return out
+
+    def render_ids(self, cam: Camera, params: Params, want_depth: bool = True):
+        """vrt_render_ids: what the frame of (cam, params) shows, per pixel and without shading. Returns
+        (ids, depth): ids[H, W] of PIXEL_ID_DTYPE, whose voxel_index and face equal pick()'s record of
+        each pixel (hit_normal, hit_cell and adjacent_cell read them), and depth[H, W] float32, the
+        parameter of the hit face's plane along the normalised primary ray from its near-plane point
+        (+inf for a miss), or None with want_depth=False. Row 0 is the bottom row."""
+        ids = np.empty((cam.height, cam.width), dtype=PIXEL_ID_DTYPE)
+        depth = np.empty((cam.height, cam.width), np.float32) if want_depth else None
+        self._check(self._lib.vrt_render_ids(self._h, C.byref(cam), C.byref(params), ids.ctypes.data,
+                                             depth.ctypes.data if want_depth else None), "vrt_render_ids")
+        return ids, depth
+
+    def render_ids_async(self, cam: Camera, params: Params, row0: int, rows: int, pitch: int, d_ids: int,
+                         d_depth: int = 0, stream: int = 0):
+        """vrt_render_ids_async: rows [row0, row0 + rows) into device buffers (e.g. torch tensors'
+        data_ptr()), pixel (px, row0 + i) at record i * pitch + px of d_ids (8-byte records) and of
+        d_depth (float32; 0: no depth), one kernel launch enqueued on a HIP stream: no host
+        synchronisation, no allocation."""
+        self._check(self._lib.vrt_render_ids_async(self._h, C.byref(cam), C.byref(params), row0, rows, pitch,
+                                                   d_ids or None, d_depth or None, stream or None),
+                    "vrt_render_ids_async")
+
+    def ids_deferred(self):
+        """vrt_ids_deferred: (pixels, deferred) of the last render_ids: how many pixels it rendered and
+        how many of them took the exact kernel (all of them: there is no certified ID kernel yet)."""
+        px, de = C.c_uint64(), C.c_uint64()
+        self._check(self._lib.vrt_ids_deferred(self._h, C.byref(px), C.byref(de)), "vrt_ids_deferred")
+        return int(px.value), int(de.value)
 
     def debug_packed_volume(self) -> np.ndarray:
         """The kernel's device volumes [octant][z][y][x] ((N+1)^3 u16 voxel | G << 8 each; 8

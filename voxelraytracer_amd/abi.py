@@ -139,6 +139,15 @@ class RayColor(C.Structure):
 # numpy dtype of one vrt_ray_color record (it starts with a vrt_hit)
 RAY_COLOR_DTYPE = HIT_DTYPE + [("rgba", "<f4", (4,))]
 
+
+# ID and depth pass (vrt_render_ids*)
+class PixelId(C.Structure):
+    _fields_ = [("voxel_index", C.c_int32), ("face", C.c_uint32)]
+
+
+# numpy dtype of one vrt_pixel_id record (vrt_ray_hit's fields of the same names)
+PIXEL_ID_DTYPE = [("voxel_index", "<i4"), ("face", "<u4")]
+
 # name -> (restype, argtypes): every function include/vrt.h declares
 # entry points added after ABI v12 (an older build loaded by VRT_LIB with VRT_LIB_ABI=<its version>
 # may lack exactly these)
@@ -148,7 +157,9 @@ ADDED_IN = {"vrt_render_temporal_batch_async": 14, "vrt_set_cert_trees": 15,
             # added within v15 after the edits (ray queries)
             "vrt_cast_rays_async": 16, "vrt_cast_rays": 16, "vrt_pick_pixels": 16,
             # added within v15 after the ray queries (shaded ray queries)
-            "vrt_trace_rays_async": 16, "vrt_trace_rays": 16, "vrt_trace_pixels": 16}
+            "vrt_trace_rays_async": 16, "vrt_trace_rays": 16, "vrt_trace_pixels": 16,
+            # added within v15 after the shaded ray queries (ID and depth pass)
+            "vrt_render_ids_async": 16, "vrt_render_ids": 16, "vrt_ids_deferred": 16}
 
 SIGNATURES = {
     "vrt_abi_version": (C.c_int, []),
@@ -193,6 +204,11 @@ SIGNATURES = {
     "vrt_trace_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(Params), C.c_void_p]),
     "vrt_trace_pixels": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.c_void_p, C.c_int32,
                                    C.c_void_p]),
+    # added within v15 (detect by symbol lookup): ID and depth pass
+    "vrt_render_ids_async": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.c_int32, C.c_int32,
+                                       C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vrt_render_ids": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.c_void_p, C.c_void_p]),
+    "vrt_ids_deferred": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "vrt_build_scene_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p]),
     "vrt_debug_packed_volume": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
     "vrt_debug_collectives": (C.c_int, [C.c_void_p]),

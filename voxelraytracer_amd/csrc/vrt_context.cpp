@@ -172,6 +172,12 @@ struct vrt_ctx {
   void* d_query_in = nullptr;
   vrt_ray_hit* d_query_out = nullptr;
   size_t query_cap = 0;
+  // first device: staging of the synchronous ID and depth pass (vrt_render_ids): ids_stage_px records and
+  // depths, grown to the largest frame. ids_pixels / ids_deferred: of the last such call (vrt_ids_deferred)
+  vrt_pixel_id* d_ids_stage = nullptr;
+  float* d_depth_stage = nullptr;
+  size_t ids_stage_px = 0;
+  uint64_t ids_pixels = 0, ids_deferred = 0;
   // ABI v12: this process's rank of a one-process-per-GPU job (vrt_comm_join): one RCCL
   // communicator per lane, so that frames in flight on different lane streams gather without
   // ordering each other (a communicator's operations run in issue order)
@@ -1234,6 +1240,8 @@ void vrt_destroy(vrt_ctx* c) {
     if (c->h_stage) (void)hipHostFree(c->h_stage);
     if (c->d_query_in) (void)hipFree(c->d_query_in);
     if (c->d_query_out) (void)hipFree(c->d_query_out);
+    if (c->d_ids_stage) (void)hipFree(c->d_ids_stage);
+    if (c->d_depth_stage) (void)hipFree(c->d_depth_stage);
     if (!c->lt_ev.empty()) (void)hipDeviceSynchronize();
     for (hipEvent_t e : c->lt_ev) (void)hipEventDestroy(e);
   }
@@ -1723,6 +1731,93 @@ int vrt_pick_pixels(vrt_ctx* ctx, const vrt_camera* cam, const vrt_params* p, co
   a.vdiv_ok = vertex_div_ranges_ok(a.inv_pv) ? 1u : 0u;
   return run_query_staged(ctx, a, vrt::kQueryPick, false, pixels, size_t(count) * 2 * sizeof(int32_t), size_t(count),
                           hits);
+}
+
+// ---- ID and depth pass (vrt_ids_kernels.h) -----------------------------------------------------
+
+// Arguments shared by vrt_render_ids*, in the pick's order. rows / pitch: the band (the synchronous form
+// passes the whole frame's); device: the buffers' alignment is checked (the kernels' 8- and 4-byte stores)
+static int check_ids(vrt_ctx* ctx, const vrt_camera* cam, const vrt_params* p, int32_t row0, int32_t rows,
+                     int64_t pitch, const void* ids, const void* depth, bool device) {
+  if (!cam || !p) return fail(ctx, VRT_ERR_INVALID, "null camera or params");
+  if (!ctx->sh[0].d_vox_pad) return fail(ctx, VRT_ERR_NO_VOLUME, "no volume uploaded");
+  if (cam->width <= 0 || cam->height <= 0 || cam->width > 32768 || cam->height > 32768)
+    return fail(ctx, VRT_ERR_INVALID, "bad image size");
+  if (rows < 0 || row0 < 0 || int64_t(row0) + rows > cam->height)
+    return fail(ctx, VRT_ERR_INVALID, "row band outside the image");
+  if (pitch < cam->width) return fail(ctx, VRT_ERR_INVALID, "row pitch must be >= the image width");
+  if (!ids) return fail(ctx, VRT_ERR_INVALID, "null id buffer");
+  if (device && ((reinterpret_cast<uintptr_t>(ids) & 7u) != 0 || (reinterpret_cast<uintptr_t>(depth) & 3u) != 0))
+    return fail(ctx, VRT_ERR_INVALID, "device id buffer must be 8-byte aligned, depth buffer 4-byte aligned");
+  return VRT_OK;
+}
+
+// One ID pass over rows [row0, row0 + rows) (rows >= 1) on `st`: one launch of the exact ID kernel, no
+// allocation, no host synchronisation
+static int enqueue_ids(vrt_ctx* ctx, const vrt_camera* cam, const vrt_params* p, int32_t row0, int32_t rows,
+                       int32_t pitch, vrt_pixel_id* d_ids, float* d_depth, hipStream_t st) {
+  Shard& s = ctx->sh[0];
+  // the frame's argument block, as the frame launches fill it (launch): primary_ray reads it
+  vrt::KArgs a = make_args(ctx, s, cam, p, row0, rows, 1);
+  a.vdiv_ok = vertex_div_ranges_ok(a.inv_pv) ? 1u : 0u;
+  a.pitch = pitch;
+  hipEvent_t eb, ee;
+  launch_timing_events(ctx, eb, ee);
+  vrt::launch_render_ids(a, s.d_vox_pad, d_ids, d_depth, st, eb, ee);
+  VRT_HIP(ctx, hipGetLastError());
+  return VRT_OK;
+}
+
+int vrt_render_ids_async(vrt_ctx* ctx, const vrt_camera* cam, const vrt_params* p, int32_t row0, int32_t rows,
+                         int32_t pitch, vrt_pixel_id* d_ids, float* d_depth, void* hip_stream) {
+  if (!ctx) return VRT_ERR_INVALID;
+  const int st = check_ids(ctx, cam, p, row0, rows, pitch, d_ids, d_depth, true);
+  if (st != VRT_OK || rows == 0) return st;
+  return enqueue_ids(ctx, cam, p, row0, rows, pitch, d_ids, d_depth, static_cast<hipStream_t>(hip_stream));
+}
+
+int vrt_render_ids(vrt_ctx* ctx, const vrt_camera* cam, const vrt_params* p, vrt_pixel_id* ids, float* depth) {
+  if (!ctx) return VRT_ERR_INVALID;
+  int st = check_ids(ctx, cam, p, 0, cam ? cam->height : 0, cam ? cam->width : 0, ids, depth, false);
+  if (st != VRT_OK) return st;
+  DeviceGuard guard;
+  Shard& s = ctx->sh[0];
+  VRT_HIP(ctx, hipSetDevice(s.device));
+  const size_t px = size_t(cam->width) * size_t(cam->height);
+  // the staging: synchronous calls only, so no launch still writes buffers that are replaced here
+  if (ctx->ids_stage_px < px) {
+    if (ctx->d_ids_stage) (void)hipFree(ctx->d_ids_stage);
+    if (ctx->d_depth_stage) (void)hipFree(ctx->d_depth_stage);
+    ctx->d_ids_stage = nullptr;
+    ctx->d_depth_stage = nullptr;
+    ctx->ids_stage_px = 0;
+    if (hipMalloc(&ctx->d_ids_stage, px * sizeof(vrt_pixel_id)) != hipSuccess ||
+        hipMalloc(&ctx->d_depth_stage, px * sizeof(float)) != hipSuccess) {
+      if (ctx->d_ids_stage) (void)hipFree(ctx->d_ids_stage);
+      ctx->d_ids_stage = nullptr;
+      ctx->d_depth_stage = nullptr;
+      return fail(ctx, VRT_ERR_OOM, "hipMalloc ID pass staging");
+    }
+    ctx->ids_stage_px = px;
+  }
+  hipStream_t qs = main_stream(s);
+  st = enqueue_ids(ctx, cam, p, 0, cam->height, cam->width, ctx->d_ids_stage, depth ? ctx->d_depth_stage : nullptr, qs);
+  if (st != VRT_OK) return st;
+  VRT_HIP(ctx, hipMemcpyAsync(ids, ctx->d_ids_stage, px * sizeof(vrt_pixel_id), hipMemcpyDeviceToHost, qs));
+  if (depth) VRT_HIP(ctx, hipMemcpyAsync(depth, ctx->d_depth_stage, px * sizeof(float), hipMemcpyDeviceToHost, qs));
+  VRT_HIP(ctx, hipStreamSynchronize(qs));
+  // no certified ID kernel yet: every pixel takes the exact kernel, on every layout
+  ctx->ids_pixels = px;
+  ctx->ids_deferred = px;
+  return VRT_OK;
+}
+
+int vrt_ids_deferred(vrt_ctx* ctx, uint64_t* pixels, uint64_t* deferred) {
+  if (!ctx) return VRT_ERR_INVALID;
+  if (!pixels || !deferred) return fail(ctx, VRT_ERR_INVALID, "null output");
+  *pixels = ctx->ids_pixels;
+  *deferred = ctx->ids_deferred;
+  return VRT_OK;
 }
 
 // ---- shaded ray queries (vrt_trace_kernels.h) --------------------------------------------------

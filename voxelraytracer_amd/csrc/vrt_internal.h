@@ -121,6 +121,11 @@ void launch_ray_query(const KArgs& a, int32_t kind, const uint16_t* vox, const v
 constexpr int32_t kTraceRays = 0, kTracePixels = 1;
 void launch_ray_trace(const KArgs& a, int32_t kind, const uint16_t* vox, const void* in, uint32_t count,
                       vrt_ray_color* out, hipStream_t s, hipEvent_t ev_begin = nullptr, hipEvent_t ev_end = nullptr);
+// ids_exact_kernel (vrt_ids_kernels.h): rows [a.row0, a.row0 + a.rows) of the frame `a` describes (make_args
+// with row_step 1; a.pitch pixels between rows of ids / depth; depth may be null), one launch, an 8x8 tile per
+// one-wave workgroup. ev_begin / ev_end: optional device timestamps, as launch_render's
+void launch_render_ids(const KArgs& a, const uint16_t* vox, vrt_pixel_id* ids, float* depth, hipStream_t s,
+                       hipEvent_t ev_begin = nullptr, hipEvent_t ev_end = nullptr);
 // fold the counter replicas into dst (accumulating) and re-zero them
 void launch_reduce_counters(unsigned long long* rep, unsigned long long* dst, hipStream_t s);
 // in-place edit of the box [lo, lo + ext) (vrt_update_volume_region), inside [0, N)^3:

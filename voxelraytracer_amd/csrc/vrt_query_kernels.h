@@ -10,6 +10,13 @@ namespace vrt {
 
 constexpr int kQueryWg = 64 * kQueryWgWaves;  // kQueryWgWaves: vrt_tuning.h
 
+// vrt_ray_hit::face (and vrt_pixel_id::face) of a march's outcome: 0 for a miss
+__device__ __forceinline__ uint32_t ray_hit_face(const Hit& h) {
+  // the normal has one non-zero component, -sign(dir[axis])
+  const bool neg = h.normal.x + h.normal.y + h.normal.z < 0.0f;
+  return h.found ? uint32_t(h.axis) | (neg ? 4u : 0u) | (h.voxel << 8) : 0u;
+}
+
 // KIND: VRT_CAST_NEAREST (RayMarch of a ray in air: march<.., PRIMARY>), VRT_CAST_OCCLUSION
 // (RayMarchShadow along the ray's own direction: skip_walk<SHADOW>, or the literal dda_walk when a
 // component is zero, tiny or huge, as walk_shadow chooses for the sun), kQueryPick (the primary ray of
@@ -75,9 +82,7 @@ __global__ void __launch_bounds__(kQueryWg) ray_query_kernel(KArgs a, const uint
     r1 = make_uint4(0u, 0u, 0u, 0u);
   } else {
     const Hit h = march<true, false, true>(c, ray, k, steps, flags);  // a miss leaves h's fields zero
-    // the normal has one non-zero component, -sign(dir[axis])
-    const bool neg = h.normal.x + h.normal.y + h.normal.z < 0.0f;
-    const uint32_t face = h.found ? uint32_t(h.axis) | (neg ? 4u : 0u) | (h.voxel << 8) : 0u;
+    const uint32_t face = ray_hit_face(h);
     r0 = make_uint4(uint32_t(h.found ? h.vidx : -1), __float_as_uint(h.len), steps, flags);
     r1 = make_uint4(__float_as_uint(h.point.x), __float_as_uint(h.point.y), __float_as_uint(h.point.z), face);
   }

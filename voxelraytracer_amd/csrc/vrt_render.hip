@@ -2,9 +2,9 @@
 // C-ABI context around them is vrt_context.cpp (include/vrt.h). One translation unit: this file
 // holds the pixel epilogue, the tile order, the primary ray, the bounce-stack exact_pixel, the two
 // frame kernels and the host launch wrappers; the rest is in the headers included below, in
-// dependency order (vrt_tuning.h through vrt_internal.h), and in vrt_query_kernels.h and
-// vrt_trace_kernels.h (the ray-query and shaded ray-query kernels, included after the primary ray and
-// exact_pixel they call).
+// dependency order (vrt_tuning.h through vrt_internal.h), and in vrt_query_kernels.h,
+// vrt_trace_kernels.h and vrt_ids_kernels.h (the ray-query, shaded ray-query and ID-pass kernels,
+// included after the primary ray and exact_pixel they call).
 //
 // One work-item per pixel; a 128-thread workgroup covers a 16x8 pixel tile and each wave64 an
 // 8x8 sub-tile, so the 64 rays of a wave start coherent. Every float operation of the DDA is
@@ -670,6 +670,8 @@ __global__ void __launch_bounds__(64, WAVES) exact_pass_kernel(KArgs a, const ui
 #include "vrt_query_kernels.h"
 // the shaded ray-query kernels (vrt_trace_rays*, vrt_trace_pixels): after exact_pixel, which they call
 #include "vrt_trace_kernels.h"
+// the ID and depth pass (vrt_render_ids*): after primary_ray and the ray-query kernel's ray_hit_face
+#include "vrt_ids_kernels.h"
 
 namespace vrt {
 
@@ -767,6 +769,16 @@ void launch_ray_trace(const KArgs& a, int32_t kind, const uint16_t* vox, const v
                           reinterpret_cast<uint4*>(out));
   else
     hipLaunchKernelGGL(kern, grid, dim3(kTraceWg), 0, s, a, vox, in, count, reinterpret_cast<uint4*>(out));
+}
+
+void launch_render_ids(const KArgs& a, const uint16_t* vox, vrt_pixel_id* ids, float* depth, hipStream_t s,
+                       hipEvent_t ev_begin, hipEvent_t ev_end) {
+  const dim3 grid(uint32_t(a.width + 7) / 8u, uint32_t(a.rows + 7) / 8u);
+  if (ev_begin || ev_end)
+    hipExtLaunchKernelGGL(ids_exact_kernel, grid, dim3(64), 0, s, ev_begin, ev_end, 0, a, vox,
+                          reinterpret_cast<uint2*>(ids), depth);
+  else
+    hipLaunchKernelGGL(ids_exact_kernel, grid, dim3(64), 0, s, a, vox, reinterpret_cast<uint2*>(ids), depth);
 }
 
 void launch_reduce_counters(unsigned long long* rep, unsigned long long* dst, hipStream_t s) {
