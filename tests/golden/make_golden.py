@@ -6,7 +6,8 @@ independent NumPy restatement (tests/test_oracle_crosscheck.py). The reference s
 vectors and cannot run here, so these pin REGRESSIONS of the restatement and the
 kernel, not the reference's own output. Each fixture holds its inputs (scene id, N, seed, camera
 matrix, params) and outputs (RGBA float32, primary hit records, counters) plus the SHA-256 of the
-volume bytes, which pins the scene builders (main.cpp:218-288).
+volume bytes, which pins the scene builders (main.cpp:218-288) and, for a scene named
+"adversarial/<name>", the volume generator of tests/adversarial_volumes.py.
 Usage: python tests/golden/make_golden.py [fixture names]
 """
 import hashlib
@@ -19,9 +20,11 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
+sys.path.insert(1, os.path.dirname(HERE))
 
 import oracle  # noqa: E402
 import voxelraytracer_amd as vrt  # noqa: E402
+from adversarial_volumes import base_params, camera_poses, scene_volume  # noqa: E402
 
 FIXTURES = [
     # name, scene, N, W, H, R, T, extra params
@@ -43,6 +46,12 @@ FIXTURES = [
     ("textured_ref_refraction32_96x64", "refraction", 32, 96, 64, 4, 4, dict(atlas="ref")),
     ("textured_ref_glass_cube16_64", "glass_cube", 16, 64, 64, 4, 4,
      dict(atlas="ref", reflection_noise=0.05, time=2.0)),
+    # adversarial volumes (tests/adversarial_volumes.py) from the generic pose inside the volume (c3),
+    # with that module's base params: material bytes up to 255; glass beside glass and beside opaque
+    ("adversarial_bytes16_64x48", "adversarial/bytes", 16, 64, 48, 4, 4,
+     dict(camera_poses(16)["c3"], reflection_noise=base_params().reflection_noise, time=base_params().time)),
+    ("adversarial_glass_clutter16_64x48", "adversarial/glass_clutter", 16, 64, 48, 4, 4,
+     dict(camera_poses(16)["c3"], reflection_noise=base_params().reflection_noise, time=base_params().time)),
 ]
 
 
@@ -72,7 +81,7 @@ def main(only=()):
             size, ts, seed = atlas_spec
             atlas = vrt.make_atlas(size, ts, seed)
             p = vrt.textured_params(p, atlas, ts)
-        vox = vrt.build_scene(scene, n)
+        vox = scene_volume(scene, n)
         rgba, hits, cnt = oracle.render(cam, vox, n, p, threads=8)
         params = {k: getattr(p, k) for k in PARAM_KEYS}
         params["sun_dir"] = list(p.sun_dir)

@@ -11,6 +11,7 @@ import pytest
 
 import oracle
 import voxelraytracer_amd as vrt
+from adversarial_volumes import scene_volume
 from voxelraytracer_amd import abi
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -31,7 +32,7 @@ def load(path):
             setattr(p, k, v)
     if "atlas" in z.files and z["atlas"].size:
         p = vrt.textured_params(p, z["atlas"], meta["params"]["atlas_texture_size"])
-    vox = vrt.build_scene(meta["scene"], meta["n"], meta["seed"])
+    vox = scene_volume(meta["scene"], meta["n"], meta["seed"])
     return z, meta, cam, p, vox
 
 
