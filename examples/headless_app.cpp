@@ -16,6 +16,7 @@
 //   - --pipelined: the display path. Frames stay on the device (vrt_render_frame_device, where a
 //     texture upload for display would consume them) with no per-frame host sync, so consecutive
 //     frames overlap on the GPU; GPU time per frame = hipEvents around the timed frames / count.
+//     Untimed frames for --device-warmup-ms (200) come first, as in bench.py: the engine clock's ramp.
 //     The default synchronous loop waits for every frame like the reference's blocking
 //     GL_TIME_ELAPSED readback (main.cpp:352-356) and reports each frame's own GPU time.
 //   - Utils::Screenshot of the last frame (key F1, :424-428) -> a binary PPM (--ppm), and the raw
@@ -50,6 +51,10 @@ struct Options {
   bool quiet = false, counters = false, pipelined = false, caller_stream = false;
   uint32_t device_mask = 1;  // bit i = HIP device i
   int warmup = 0;            // frames excluded from the reported mean
+  // --pipelined: untimed frames rendered for this long before frame 0, as bench.py's
+  // --device-warmup-ms: the engine clock ramps up over the first ~150 ms of this load, and a run of a
+  // few hundred C3 frames (15 ms) would be timed inside the ramp, 6-10 % below sustained rendering
+  float device_warmup_ms = 200.0f;
   int pick_x = -1, pick_y = -1;  // --pick: pixel (x, y = frame row, 0 = bottom) picked after the last frame
 };
 
@@ -60,6 +65,8 @@ void usage() {
       "             [--refraction-noise x] [--day-night SECONDS_PER_FRAME] [--reset-at K]\n"
       "             [--atlas-raw FILE --atlas-size S --atlas-tile T] [--ppm FILE] [--raw FILE]\n"
       "             [--device-mask M] [--counters] [--warmup K] [--pipelined [--caller-stream]] [--quiet]\n"
+      "             [--device-warmup-ms MS]   --pipelined: untimed frames for MS ms before frame 0 (200;\n"
+      "                            the clocks' ramp-up; the history is cleared after them)\n"
       "             [--pick X,Y]   after the last frame, print what pixel (X, Y) (Y = 0: bottom row) shows:\n"
       "                            pick X Y voxel=<index> byte=<b> len=<length> face=<+|-><x|y|z> cell=<i>,<j>,<k>\n"
       "                            (the sky: voxel=-1 byte=0 len=0 face=none cell=none)");
@@ -100,6 +107,7 @@ bool parse(int argc, char** argv, Options& o) {
     else if (a == "--caller-stream") o.caller_stream = true;
     else if (a == "--device-mask") o.device_mask = uint32_t(std::strtoul(next(a.c_str()), nullptr, 0));
     else if (a == "--warmup") o.warmup = std::atoi(next("--warmup"));
+    else if (a == "--device-warmup-ms") o.device_warmup_ms = std::strtof(next(a.c_str()), nullptr);
     else if (a == "--pick") {
       if (std::sscanf(next("--pick"), "%d,%d", &o.pick_x, &o.pick_y) != 2) return false;
     }
@@ -239,6 +247,22 @@ int main(int argc, char** argv) {
     }
     hipStream_t cs = o.caller_stream ? s : nullptr;
     auto t0 = std::chrono::steady_clock::now();
+    // device warm-up: the first frame over and over until the time is up (the host runs at most the
+    // ring's frames ahead, so the clock is read every few frames' GPU time), then a fresh history:
+    // the frames that follow are those of a run without it
+    if (o.device_warmup_ms > 0.0f) {
+      p.time = 1.0f;
+      vrt_sun_dir(time_of_day, day_time, p.sun_dir);
+      while (status == 0 &&
+             std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() < o.device_warmup_ms) {
+        if (vrt_render_frame_device(rt, &cam, &p, o.alpha, cs, &d_frame, nullptr) != VRT_OK) {
+          std::fprintf(stderr, "vrt_render_frame_device: %s\n", vrt_last_error(rt));
+          status = 1;
+        }
+      }
+      if (hipDeviceSynchronize() != hipSuccess) status = 1;
+      vrt_history_reset(rt);
+    }
     for (int f = 0; f < o.frames && status == 0; ++f) {
       if (f == o.warmup) {
         if (cs) {

@@ -87,7 +87,31 @@ typedef struct {
   float eu;     /* bound of the exact walk's parameter error there */
   int iters, jumps;
   int why;      /* reason of UNC */
+  int exitc;    /* the way out of the loop (X_*) */
+  int corner;   /* the walk passed a corner block (2x2x2 alternatives, none an event) and went on */
 } cres_t;
+
+/* The ways out of the kernel's walk loop (cert_walk, csrc/vrt_cert.h), tallied per walk kind by
+ * cs_run for cs_exits. X_LEN_TIE is classified only: the kernel returns unsure there, the model
+ * keeps its miss. X_CORNER_IN counts walks that passed a corner block and went on. */
+enum { X_NONE = 0, X_HIT, X_HIT_ONE_FLAG, X_EVENT_FLAGS, X_EVENT_LEN, X_CORNER, X_AHEAD, X_BEHIND,
+       X_LEN_MISS, X_LEN_TIE, X_OUTSIDE, X_CAP, X_CORNER_IN, X_COUNT };
+static long XT[2][X_COUNT];
+EXPORT void cs_exits_reset(void) { memset(XT, 0, sizeof XT); }
+/* out[kind * X_COUNT + class]: kind 0 primary walks, 1 shadow walks; returns X_COUNT */
+EXPORT int cs_exits(double* out) {
+  for (int k = 0; k < 2; k++)
+    for (int q = 0; q < X_COUNT; q++) out[k * X_COUNT + q] = (double)XT[k][q];
+  return X_COUNT;
+}
+static void tally(int kind, const cres_t* r) {
+#pragma omp atomic
+  XT[kind][r->exitc]++;
+  if (r->corner) {
+#pragma omp atomic
+    XT[kind][X_CORNER_IN]++;
+  }
+}
 
 static const double U24 = 1.0 / 16777216.0;
 
@@ -171,7 +195,18 @@ static cres_t cwalk(v3 P, v3 D, float U, int shadow, const int* cell0, double e0
       float q = sig[b] - arcp[b];
       if (q > prev) prev = q;
     }
-    if ((double)prev > (double)U + gL) { r.res = C_MISS; return r; }
+    if ((double)prev > (double)U + gL) {
+      /* (the kernel's tie case: the crossing may merge into the step before, which passed the test) */
+      float mback = sig[0] - arcp[0];
+      double mg = gam[0];
+      for (int b = 1; b < 3; b++) {
+        if (sig[b] - arcp[b] > mback) mback = sig[b] - arcp[b];
+        if (gam[b] > mg) mg = gam[b];
+      }
+      r.exitc = (double)s1 - mback < 2.0 * mg ? X_LEN_TIE : X_LEN_MISS;
+      r.res = C_MISS;
+      return r;
+    }
     int nc[3] = {cell[0], cell[1], cell[2]};
     nc[a] += s[a];
     int nah = 0, nbh = 0, ah[3] = {0, 0, 0}, bh[3] = {0, 0, 0};
@@ -194,10 +229,11 @@ static cres_t cwalk(v3 P, v3 D, float U, int shadow, const int* cell0, double e0
           c2[b] += s[b];
           if (!is_event(alt_byte(c1), 1) && !is_event(alt_byte(c2), 1)) ok = 0;
         }
-        if (ok && (double)prev + gL < (double)U) { r.res = C_HIT; r.byte = path_byte(nc); r.axis = a; return r; }
+        if (ok && (double)prev + gL < (double)U) { r.res = C_HIT; r.byte = path_byte(nc); r.axis = a; r.exitc = X_HIT_ONE_FLAG; return r; }
       }
-      if (nah || nbh) { r.res = C_UNC; r.why = 2; return r; }
-      if ((double)prev + gL >= (double)U) { r.res = C_UNC; r.why = 3; return r; }
+      if (nah || nbh) { r.res = C_UNC; r.why = 2; r.exitc = X_EVENT_FLAGS; return r; }
+      if ((double)prev + gL >= (double)U) { r.res = C_UNC; r.why = 3; r.exitc = X_EVENT_LEN; return r; }
+      r.exitc = X_HIT;
       r.res = C_HIT;
       r.byte = path_byte(nc);
       r.axis = a;
@@ -210,39 +246,41 @@ static cres_t cwalk(v3 P, v3 D, float U, int shadow, const int* cell0, double e0
       for (int q = 1; q < 8; q++) {
         int c[3] = {cell[0] + ((q & 1) ? s[0] : 0), cell[1] + ((q & 2) ? s[1] : 0),
                     cell[2] + ((q & 4) ? s[2] : 0)};
-        if (is_event(alt_byte(c), shadow)) { r.res = C_UNC; r.why = 4; return r; }
+        if (is_event(alt_byte(c), shadow)) { r.res = C_UNC; r.why = 4; r.exitc = X_CORNER; return r; }
       }
       for (int b = 0; b < 3; b++) {
         if (!bh[b]) continue;
         int c[3] = {nc[0], nc[1], nc[2]};
         c[b] -= s[b];
-        if (is_event(alt_byte(c), shadow)) { r.res = C_UNC; r.why = 4; return r; }
+        if (is_event(alt_byte(c), shadow)) { r.res = C_UNC; r.why = 4; r.exitc = X_CORNER; return r; }
       }
+      r.corner = 1;
     } else {
       for (int b = 0; b < 3; b++) {
         if (ah[b]) {   /* b may be crossed first (or tie): cell + e_b; the tie cell is the path's */
           int c[3] = {cell[0], cell[1], cell[2]};
           c[b] += s[b];
-          if (is_event(alt_byte(c), shadow)) { r.res = C_UNC; r.why = 5; return r; }
+          if (is_event(alt_byte(c), shadow)) { r.res = C_UNC; r.why = 5; r.exitc = X_AHEAD; return r; }
           int c2[3] = {nc[0], nc[1], nc[2]};
           c2[b] += s[b];
-          if (is_event(alt_byte(c2), shadow)) { r.res = C_UNC; r.why = 5; return r; }
+          if (is_event(alt_byte(c2), shadow)) { r.res = C_UNC; r.why = 5; r.exitc = X_AHEAD; return r; }
         }
         if (bh[b]) {   /* a may have been crossed before b: nc - e_b */
           int c[3] = {nc[0], nc[1], nc[2]};
           c[b] -= s[b];
-          if (is_event(alt_byte(c), shadow)) { r.res = C_UNC; r.why = 6; return r; }
+          if (is_event(alt_byte(c), shadow)) { r.res = C_UNC; r.why = 6; r.exitc = X_BEHIND; return r; }
         }
       }
     }
     /* the alternatives through a wrapped plane N are covered by alt_byte */
-    if ((s[a] > 0 && nc[a] >= N) || (s[a] < 0 && nc[a] < 0)) { r.res = C_MISS; return r; }
+    if ((s[a] > 0 && nc[a] >= N) || (s[a] < 0 && nc[a] < 0)) { r.res = C_MISS; r.exitc = X_OUTSIDE; return r; }
     cell[a] = nc[a];
     float np = (float)(cell[a] + (s[a] > 0 ? 1 : 0));
     sig[a] = (np - p[a]) * rcp[a];
   }
   r.res = C_UNC;
   r.why = 7;
+  r.exitc = X_CAP;
   return r;
 }
 
@@ -299,6 +337,7 @@ EXPORT void cs_run(const float* inv_pv, int w, int h, const float* sun, float ma
         loc[1] += steps;
         int unc = 0, uncp = 0;
         cres_t cr = cwalk(ray.pos, ray.dir, max_len - 0.0f, 0, NULL, 0.0, (double[3]){0, 0, 0}, 0.0);
+        tally(0, &cr);
         loc[2] += cr.iters;
         { uint16_t* w = &wave_it[(py / 8) * tw + px / 8]; if (cr.iters > *w) *w = (uint16_t)cr.iters; }
         loc[3] += cr.jumps;
@@ -362,6 +401,7 @@ EXPORT void cs_run(const float* inv_pv, int w, int h, const float* sun, float ma
             if (!okst) { loc[13] += 1; unc = 1; }
             else {
               cres_t cs = cwalk(X, sr.dir, max_len - is.len, 1, c0, eH, ed, xu);
+              tally(1, &cs);
               loc[14] += cs.iters;
               { uint16_t* w = &wave_its[(py / 8) * tw + px / 8]; if (cs.iters > *w) *w = (uint16_t)cs.iters; }
               loc[15] += cs.jumps;

@@ -35,6 +35,7 @@ namespace vrt {
 // exact walk, and textured shading reads the hit point.
 
 enum : int { CERT_MISS = 0, CERT_HIT = 1, CERT_UNSURE = 2 };
+constexpr int kCertRun = 3;  // inside cert_walk's loop: the walk goes on
 constexpr float kCertMargin = 1.0f / 64.0f;  // jump boxes' forward faces pulled in (position)
 constexpr int kCertMaxIter = 1024;
 constexpr float kCertMaxOrigin = 4e-3f;  // parameter uncertainty of a secondary start beyond which: unsure
@@ -191,6 +192,13 @@ __device__ __forceinline__ CertResult cert_walk(const Ctx& c, const f3 P, const 
   CTRACE(c, 100 + int(SHADOW), cx, cy, cz, P.x, P.y, P.z, U);
   CTRACE(c, 101, D.x, D.y, D.z, e0, ed.x, ed.y, ed.z);
   CERT_DIAG_ONLY(r.iters = 0;)
+  if (LEAN && PHASE_STOP(SHADOW ? 4 : 2)) {  // phase budget: the prologue's values into the result
+    r.u = ((sig.x + sig.y) + (sig.z + q2)) + ((a1 + b1) + (b0 + c0)) + ((g2 + g1) + (g0 + Ps.x)) +
+          ((Ps.y + Ps.z) + (Da.x + Da.y)) + ((Da.z + ar.x) + (ar.y + ar.z)) + U;
+    r.cx = int(tex + obase) + mx + my + mz;
+    return r;
+  }
+  int st = CERT_UNSURE;
   for (int guard = 0; guard < kCertMaxIter; ++guard) {
     CERT_DIAG_ONLY(r.iters = guard + 1;)
     const float s1 = __builtin_fminf(sig.x, __builtin_fminf(sig.y, sig.z));
@@ -261,143 +269,174 @@ __device__ __forceinline__ CertResult cert_walk(const Ctx& c, const f3 P, const 
     // (the crossing reads sig after the jump's merge, and the axis from it: the planes then live in
     // one set of registers across the iteration; with `continue` in the jump two of them were
     // copied out and back in every iteration)
-    if (jumped) continue;
-    const int a = sig.x == s1 ? 0 : (sig.y == s1 ? 1 : 2);
-    // one crossing, s1 on axis a; prev = the crossing before it (the exact walk's len there)
-    const f3 gam = mk(gam_of(ar.x, ed.x), gam_of(ar.y, ed.y), gam_of(ar.z, ed.z));
-    const f3 back = mk(sig.x - ar.x, sig.y - ar.y, sig.z - ar.z);
-    const float mback = gmax(back.x, gmax(back.y, back.z));
-    const float prev = gmax(mback, 0.0f);
-    const float gL = __builtin_fmaf(__builtin_fmaf(g2, uu, g1), uu, g0);
-    if (prev > U + gL) {
-      // the length test stops the walk before this crossing, unless a tie merges it into the
-      // step of the one before (that step passed the test): then the exact walk still samples it
-      // (a tree ray whose y and z crossings tied at len 101.1 left the glass there, refracting,
-      // before its length ended the march; its sky colour took the refracted direction)
-      if (s1 - mback < 2.0f * gmax(gam.x, gmax(gam.y, gam.z))) return r;
-      r.res = CERT_MISS;
-      return r;
-    }
-    const int nx = cx + (a == 0 ? sx : 0), ny = cy + (a == 1 ? sy : 0), nz = cz + (a == 2 ? sz : 0);
-    const uint32_t ntex = LEAN ? cross_texel(c, nx, ny, nz, obase) : path_texel(c, nx, ny, nz, obase);
-    const float ga = a == 0 ? gam.x : (a == 1 ? gam.y : gam.z);
-    // near-edge flags per other axis: ahead (crossed within the bound after s1) / behind (before).
-    // A plane behind counts down to -gam_b, not 0: a ray that starts ON a plane (a shadow or
-    // secondary ray from an exact hit point on the hit face) has that plane at parameter 0 up to
-    // rounding, and the exact walk's currentPos stays on it — sampling the voxel beyond it — until
-    // the ray has moved half an ulp of the coordinate off it (r02 s18: a shadow ray from
-    // (33.000008, 127, 37.02) sampled the panel voxel (32, 127, 37) at its first x crossing, and
-    // back.y rounded to just below 0 hid that alternative from the certified walk)
-    // nf bits 0-2: ahead x, y, z; 3-5: behind x, y, z. They are rare: a superset test first (the
-    // second smallest sig bounds every sig_b, b != a, from below, the latest back every back_b from
-    // above, and ga + max gam every ga + gam_b; rounding is monotone), the flags only if it holds.
-    const float tg = ga + gmax(gam.x, gmax(gam.y, gam.z));
-    // the crossings up to prev are settled (this one, at s1, may not be): an exact step at s <
-    // prev - tg has its real crossing before prev (gam_b <= tg), so it samples a settled cell
-    r.us = prev - tg - 1e-3f;
-    uint32_t nf = 0u;
-    if (__builtin_amdgcn_fmed3f(sig.x, sig.y, sig.z) - s1 < tg || s1 - mback < tg) {
-      const bool ahx = a != 0 && sig.x - s1 < ga + gam.x, ahy = a != 1 && sig.y - s1 < ga + gam.y,
-                 ahz = a != 2 && sig.z - s1 < ga + gam.z;
-      const bool bhx = a != 0 && back.x > -gam.x && s1 - back.x < ga + gam.x;
-      const bool bhy = a != 1 && back.y > -gam.y && s1 - back.y < ga + gam.y;
-      const bool bhz = a != 2 && back.z > -gam.z && s1 - back.z < ga + gam.z;
-      nf = uint32_t(ahx) | uint32_t(ahy) << 1 | uint32_t(ahz) << 2 | uint32_t(bhx) << 3 |
-           uint32_t(bhy) << 4 | uint32_t(bhz) << 5;
-    }
-    const uint32_t nb = ntex & kVoxMask;
-    CTRACE(c, 103, nx, ny, nz, s1, a, nf, nb);
-    CTRACE(c, 104, cx, cy, cz, sig.x, sig.y, sig.z, ga);
-    if (cert_event<SHADOW>(nb, medium)) {
-      if (!(prev + gL < U)) return r;  // the length test might stop the walk first
-      if (nf == 0u) {
-        r.res = CERT_HIT;
-        r.byte = nb;
-        r.axis = a;
-        r.cx = nx;
-        r.cy = ny;
-        r.cz = nz;
-        r.u = s1;
-        r.eu = ga;
-        return r;
-      }
-      if (SHADOW && __builtin_popcount(nf) == 1) {
-        // blocked whichever way the exact walk goes: near-behind b still samples nc (or nc - e_b
-        // first); near-ahead b samples nc, or cell + e_b and then nc + e_b
-        bool ok = true;
-        if (nf & 7u) {
-          const int bx = (nf & 1u) ? sx : 0, by = (nf & 2u) ? sy : 0, bz = (nf & 4u) ? sz : 0;
-          ok = cert_event<true>(alt_byte(c, cx + bx, cy + by, cz + bz, obase), 0u) ||
-               cert_event<true>(alt_byte(c, nx + bx, ny + by, nz + bz, obase), 0u);
-        }
-        if (ok) {
-          r.res = CERT_HIT;
-          r.byte = nb;
-        }
-      }
-      return r;  // hit or unsure
-    }
-    if (nf) {  // cells the exact walk may sample instead of the path's: all must be non-events
-      const bool ahx = nf & 1u, ahy = nf & 2u, ahz = nf & 4u, bhx = nf & 8u, bhy = nf & 16u,
-                 bhz = nf & 32u;
-      const int nah = int(ahx) + int(ahy) + int(ahz);
-      // LEAN: each rare block below decodes a flag where it uses it, from a fresh opaque copy of nf,
-      // instead of the six lane masks above (both polarities) being kept across the blocks' loads:
-      // they were the walk's SGPR spills, 24 of the hot instance's 61
-      auto flag = [&](int bit, bool decoded) {
-        if constexpr (LEAN) {
-          uint32_t f = nf;
-          asm volatile("" : "+v"(f));
-          return ((f >> bit) & 1u) != 0u;
+    // One exit (r09): the crossing below has no `return`. It decides this iteration's outcome st,
+    // kCertRun or the walk's result, and the loop's end tests it once; the result's fields are not
+    // carried through the loop (eight VGPRs, and a state variable decoded by ~25 scalar instructions
+    // in every iteration, jumps included) but read after it from the loop's own variables.
+    st = kCertRun;
+    if (!jumped) {
+      const int a = sig.x == s1 ? 0 : (sig.y == s1 ? 1 : 2);
+      // one crossing, s1 on axis a; prev = the crossing before it (the exact walk's len there)
+      const f3 gam = mk(gam_of(ar.x, ed.x), gam_of(ar.y, ed.y), gam_of(ar.z, ed.z));
+      const f3 back = mk(sig.x - ar.x, sig.y - ar.y, sig.z - ar.z);
+      const float mback = gmax(back.x, gmax(back.y, back.z));
+      const float prev = gmax(mback, 0.0f);
+      const float gL = __builtin_fmaf(__builtin_fmaf(g2, uu, g1), uu, g0);
+      // the length test stops the walk before this crossing (decided in the rare block below)
+      const bool lenstop = prev > U + gL;
+      const int nx = cx + (a == 0 ? sx : 0), ny = cy + (a == 1 ? sy : 0), nz = cz + (a == 2 ? sz : 0);
+      const uint32_t ntex = LEAN ? cross_texel(c, nx, ny, nz, obase) : path_texel(c, nx, ny, nz, obase);
+      const float ga = a == 0 ? gam.x : (a == 1 ? gam.y : gam.z);
+      // near-edge flags per other axis: ahead (crossed within the bound after s1) / behind (before).
+      // A plane behind counts down to -gam_b, not 0: a ray that starts ON a plane (a shadow or
+      // secondary ray from an exact hit point on the hit face) has that plane at parameter 0 up to
+      // rounding, and the exact walk's currentPos stays on it — sampling the voxel beyond it — until
+      // the ray has moved half an ulp of the coordinate off it (r02 s18: a shadow ray from
+      // (33.000008, 127, 37.02) sampled the panel voxel (32, 127, 37) at its first x crossing, and
+      // back.y rounded to just below 0 hid that alternative from the certified walk)
+      // nf bits 0-2: ahead x, y, z; 3-5: behind x, y, z. They are rare: a superset test first (the
+      // second smallest sig bounds every sig_b, b != a, from below, the latest back every back_b from
+      // above, and ga + max gam every ga + gam_b; rounding is monotone), the flags only if it holds.
+      const float tg = ga + gmax(gam.x, gmax(gam.y, gam.z));
+      // the crossings up to prev are settled (this one, at s1, may not be): an exact step at s <
+      // prev - tg has its real crossing before prev (gam_b <= tg), so it samples a settled cell
+      if (!lenstop) r.us = prev - tg - 1e-3f;
+      const bool near = __builtin_amdgcn_fmed3f(sig.x, sig.y, sig.z) - s1 < tg || s1 - mback < tg;
+      const uint32_t nb = ntex & kVoxMask;
+      const int na = a == 0 ? nx : (a == 1 ? ny : nz);
+      // The crossing's outcome, decided in the order: length test, event, alternatives, outside. The
+      // plain cases first, without a branch (no length stop, no near-edge flag): an event is a hit if
+      // the length test cannot stop the walk first, else unsure; a cell outside the volume (moving
+      // away on axis a) a miss; anything else goes on. The rare block below overrides them. `stop` is
+      // the loop's one way out besides its iteration cap, with the result already in res. (Both forms
+      // of the decision over every combination of its predicates: tests/test_cert_one_exit_tables.py.)
+      // The crossing's texel is loaded before the length test is looked at: its address is in bounds
+      // either way (cross_texel / path_texel), and a walk the length test stops reads it for nothing.
+      const bool ev = cert_event<SHADOW>(nb, medium);
+      const bool lenok = prev + gL < U;  // the length test cannot stop the walk before this crossing
+      const bool outside = LEAN ? cross_outside(ntex) : uint32_t(na) >= uint32_t(c.n);
+      int res = ev ? (lenok ? CERT_HIT : CERT_UNSURE) : (outside ? CERT_MISS : CERT_UNSURE);
+      bool stop = ev || outside;
+      CTRACE(c, 104, cx, cy, cz, sig.x, sig.y, sig.z, ga);
+      if (lenstop || near) {
+        if (lenstop) {
+          // the length test stops the walk before this crossing, unless a tie merges it into the
+          // step of the one before (that step passed the test): then the exact walk still samples it
+          // (a tree ray whose y and z crossings tied at len 101.1 left the glass there, refracting,
+          // before its length ended the march; its sky colour took the refracted direction)
+          stop = true;
+          res = s1 - mback < 2.0f * gmax(gam.x, gmax(gam.y, gam.z)) ? CERT_UNSURE : CERT_MISS;
         } else {
-          return decoded;
+          const bool ahx = a != 0 && sig.x - s1 < ga + gam.x, ahy = a != 1 && sig.y - s1 < ga + gam.y,
+                     ahz = a != 2 && sig.z - s1 < ga + gam.z;
+          const bool bhx = a != 0 && back.x > -gam.x && s1 - back.x < ga + gam.x;
+          const bool bhy = a != 1 && back.y > -gam.y && s1 - back.y < ga + gam.y;
+          const bool bhz = a != 2 && back.z > -gam.z && s1 - back.z < ga + gam.z;
+          const uint32_t nf = uint32_t(ahx) | uint32_t(ahy) << 1 | uint32_t(ahz) << 2 | uint32_t(bhx) << 3 |
+                              uint32_t(bhy) << 4 | uint32_t(bhz) << 5;
+          CTRACE(c, 103, nx, ny, nz, s1, a, nf, nb);
+          // LEAN: each rare block below decodes a flag where it uses it, from a fresh opaque copy of nf,
+          // instead of the six lane masks above (both polarities) being kept across the blocks' loads:
+          // they were the walk's SGPR spills, 24 of the hot instance's 61
+          auto flag = [&](int bit, bool decoded) {
+            if constexpr (LEAN) {
+              uint32_t f = nf;
+              asm volatile("" : "+v"(f));
+              return ((f >> bit) & 1u) != 0u;
+            } else {
+              return decoded;
+            }
+          };
+          if (nf != 0u && ev) {
+            // an event with flags: unsure, but for a shadow walk's one-flag hit
+            res = CERT_UNSURE;
+            if (SHADOW && lenok && __builtin_popcount(nf) == 1) {
+              // blocked whichever way the exact walk goes: near-behind b still samples nc (or nc - e_b
+              // first); near-ahead b samples nc, or cell + e_b and then nc + e_b
+              bool ok = true;
+              if (nf & 7u) {
+                const int bx = (nf & 1u) ? sx : 0, by = (nf & 2u) ? sy : 0, bz = (nf & 4u) ? sz : 0;
+                ok = cert_event<true>(alt_byte(c, cx + bx, cy + by, cz + bz, obase), 0u) ||
+                     cert_event<true>(alt_byte(c, nx + bx, ny + by, nz + bz, obase), 0u);
+              }
+              if (ok) res = CERT_HIT;
+            }
+          } else if (nf != 0u) {  // cells the exact walk may sample instead of the path's: all must be non-events
+            const int nah = int(ahx) + int(ahy) + int(ahz);
+            bool bad = false;
+            if (__builtin_popcount(nf) >= 2) {  // near a corner: the 2x2x2 block ahead and the cells behind nc
+              for (int q = 1; q < 8 && !bad; ++q)
+                bad = cert_event<SHADOW>(alt_byte(c, cx + ((q & 1) ? sx : 0), cy + ((q & 2) ? sy : 0),
+                                                  cz + ((q & 4) ? sz : 0), obase), medium);
+              bad = bad || (flag(3, bhx) && cert_event<SHADOW>(alt_byte(c, nx - sx, ny, nz, obase), medium)) ||
+                    (flag(4, bhy) && cert_event<SHADOW>(alt_byte(c, nx, ny - sy, nz, obase), medium)) ||
+                    (flag(5, bhz) && cert_event<SHADOW>(alt_byte(c, nx, ny, nz - sz, obase), medium));
+            } else if (nah) {  // b may be crossed first, or tie: cell + e_b, nc + e_b
+              const int bx = flag(0, ahx) ? sx : 0, by = flag(1, ahy) ? sy : 0, bz = flag(2, ahz) ? sz : 0;
+              bad = cert_event<SHADOW>(alt_byte(c, cx + bx, cy + by, cz + bz, obase), medium) ||
+                    cert_event<SHADOW>(alt_byte(c, nx + bx, ny + by, nz + bz, obase), medium);
+            } else {  // a may have been crossed before b: nc - e_b
+              bad = cert_event<SHADOW>(alt_byte(c, nx - (flag(3, bhx) ? sx : 0), ny - (flag(4, bhy) ? sy : 0),
+                                                nz - (flag(5, bhz) ? sz : 0), obase), medium);
+            }
+            if (bad) {  // unsure; else the plain outcome stands: outside a miss, or the walk goes on
+              stop = true;
+              res = CERT_UNSURE;
+            }
+          }
         }
-      };
-      if (__builtin_popcount(nf) >= 2) {  // near a corner: the 2x2x2 block ahead and the cells behind nc
-        for (int q = 1; q < 8; ++q)
-          if (cert_event<SHADOW>(alt_byte(c, cx + ((q & 1) ? sx : 0), cy + ((q & 2) ? sy : 0),
-                                          cz + ((q & 4) ? sz : 0), obase), medium))
-            return r;
-        if ((flag(3, bhx) && cert_event<SHADOW>(alt_byte(c, nx - sx, ny, nz, obase), medium)) ||
-            (flag(4, bhy) && cert_event<SHADOW>(alt_byte(c, nx, ny - sy, nz, obase), medium)) ||
-            (flag(5, bhz) && cert_event<SHADOW>(alt_byte(c, nx, ny, nz - sz, obase), medium)))
-          return r;
-      } else if (nah) {  // b may be crossed first, or tie: cell + e_b, nc + e_b
-        const int bx = flag(0, ahx) ? sx : 0, by = flag(1, ahy) ? sy : 0, bz = flag(2, ahz) ? sz : 0;
-        if (cert_event<SHADOW>(alt_byte(c, cx + bx, cy + by, cz + bz, obase), medium) ||
-            cert_event<SHADOW>(alt_byte(c, nx + bx, ny + by, nz + bz, obase), medium))
-          return r;
-      } else {  // a may have been crossed before b: nc - e_b
-        if (cert_event<SHADOW>(alt_byte(c, nx - (flag(3, bhx) ? sx : 0), ny - (flag(4, bhy) ? sy : 0),
-                                        nz - (flag(5, bhz) ? sz : 0), obase), medium))
-          return r;
+      }
+      // the cell entered is the walk's cell either way: a walk that stops leaves its last cell and texel
+      // (the hit's) in the loop's own variables, and its planes as they are, for the result below
+      cx = nx;
+      cy = ny;
+      cz = nz;
+      tex = ntex;
+      st = stop ? res : kCertRun;
+      if (!stop) {
+        if constexpr (LEAN) {
+          // the crossed axis' next plane, sign-folded as after a jump: s_a float(na + u_a) is float((na ^
+          // m_a) + 1) (moving down ~na + 1 = -na), so (that - Ps_a) |1/d_a| is (np - P_a) rcp_a bit for
+          // bit (not a zero either: it is s1 + |1/d_a| up to rounding). P and rcp are then dead in the loop.
+          const int ma = a == 0 ? mx : (a == 1 ? my : mz);
+          const float fp = float((na ^ ma) + 1);
+          if (a == 0) sig.x = (fp - Ps.x) * ar.x;
+          else if (a == 1) sig.y = (fp - Ps.y) * ar.y;
+          else sig.z = (fp - Ps.z) * ar.z;
+        } else {
+          const int sa = a == 0 ? sx : (a == 1 ? sy : sz);
+          const float np = float(na + (sa > 0 ? 1 : 0));
+          if (a == 0) sig.x = (np - P.x) * rcp.x;
+          else if (a == 1) sig.y = (np - P.y) * rcp.y;
+          else sig.z = (np - P.z) * rcp.z;
+        }
       }
     }
-    const int na = a == 0 ? nx : (a == 1 ? ny : nz);
-    const int sa = a == 0 ? sx : (a == 1 ? sy : sz);
-    if (LEAN ? cross_outside(ntex) : uint32_t(na) >= uint32_t(c.n)) {  // left the volume (moving away on axis a)
-      r.res = CERT_MISS;
-      return r;
-    }
-    cx = nx;
-    cy = ny;
-    cz = nz;
-    tex = ntex;
-    if constexpr (LEAN) {
-      // the crossed axis' next plane, sign-folded as after a jump: s_a float(na + u_a) is float((na ^
-      // m_a) + 1) (moving down ~na + 1 = -na), so (that - Ps_a) |1/d_a| is (np - P_a) rcp_a bit for
-      // bit (not a zero either: it is s1 + |1/d_a| up to rounding). P and rcp are then dead in the loop.
-      const int ma = a == 0 ? mx : (a == 1 ? my : mz);
-      const float fp = float((na ^ ma) + 1);
-      if (a == 0) sig.x = (fp - Ps.x) * ar.x;
-      else if (a == 1) sig.y = (fp - Ps.y) * ar.y;
-      else sig.z = (fp - Ps.z) * ar.z;
-    } else {
-      const float np = float(na + (sa > 0 ? 1 : 0));
-      if (a == 0) sig.x = (np - P.x) * rcp.x;
-      else if (a == 1) sig.y = (np - P.y) * rcp.y;
-      else sig.z = (np - P.z) * rcp.z;
-    }
+    // the loop's one exit besides its iteration cap. The outcome is kept opaque here, after the merge
+    // of the jump and the crossing, so that the test is made once, where every lane passes
+    asm volatile("" : "+v"(st));
+    if (st != kCertRun) break;
+    st = CERT_UNSURE;  // (the iteration cap: unsure)
+  }
+  // The result's fields from what the loop left: the last crossing's cell and texel, and its axis,
+  // parameter and bound recomputed from the planes it did not advance: the same operations on the
+  // same operands as in the loop (they mean something for a hit only; a shadow walk's caller reads
+  // none of them).
+  r.res = st;
+  {
+    const float s1 = __builtin_fminf(sig.x, __builtin_fminf(sig.y, sig.z));
+    const float uu = gmax(s1, 0.0f);
+    const float A = __builtin_fmaf(__builtin_fmaf(q2, uu, a1), uu, c0);
+    const float B = __builtin_fmaf(b1, uu, b0);
+    const int a = sig.x == s1 ? 0 : (sig.y == s1 ? 1 : 2);
+    const float g = __builtin_fmaf(B, a == 0 ? ar.x : (a == 1 ? ar.y : ar.z), A);
+    r.byte = tex & kVoxMask;
+    r.axis = a;
+    r.cx = cx;
+    r.cy = cy;
+    r.cz = cz;
+    r.u = s1;
+    r.eu = ED ? g + (a == 0 ? ed.x : (a == 1 ? ed.y : ed.z)) : g;
   }
   return r;
 }
@@ -481,6 +520,10 @@ __device__ __forceinline__ bool cert_shade_hit(const Ctx& c, const Ray& ray, con
     if (cert_event<true>(cell_texel(c, ax, ay, az, sob) & kVoxMask, 0u)) { CERT_DIAG(7); return false; }
     const CertResult s = cert_walk<true, LEAN>(c, hh.point, S, c.sun_rcp, c.max_len - hh.len, ax, ay, az,
                                          h.eu, ed, hh.len, 0u, t0);
+    if (LEAN && (PHASE_STOP(4) || PHASE_STOP(5))) {  // phase budget: the shadow walk's result as the colour
+      color = mk(s.u + float(s.res), lit + float(s.cx), 0.0f);
+      return true;
+    }
     if (s.res == CERT_UNSURE) { CERT_DIAG(8); return false; }
     CERT_DIAG(9);
     brightness = s.res == CERT_HIT ? kAmbient : lit;
@@ -1060,31 +1103,61 @@ __device__ __forceinline__ bool cert_texel(const Ctx& c, const Ray& ray, const C
   return true;
 }
 
+// The launch's arguments read again where the certified pass (LEAN) first needs them, after the
+// primary walk: KArgs is the kernels' first argument, at offset 0 of the kernarg segment, and the
+// pointer is kept opaque so that the scalar loads through it are not hoisted back above the walk. The
+// sun, the sky factor and the atlas constants copied into Ctx before the primary ray (init_ctx) were
+// 13 SGPRs live across the primary walk, and the frame's outputs six more across both walks: the
+// budget the certified pass's SGPR spills came from.
+typedef const __attribute__((address_space(4))) KArgs LateKArgs;
+__device__ __forceinline__ LateKArgs* late_kargs() {
+  LateKArgs* ka = (LateKArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(ka));
+  return ka;
+}
+// the Ctx fields init_ctx<true> leaves out: the same values from the same words
+__device__ __forceinline__ void late_ctx(Ctx& c) {
+  LateKArgs* ka = late_kargs();
+  c.sky_sy = ka->sky_sy;
+  c.sun_n = mk(ka->sun_n[0], ka->sun_n[1], ka->sun_n[2]);
+  c.sun_rcp = mk(ka->sun_rcp[0], ka->sun_rcp[1], ka->sun_rcp[2]);
+  c.atlas = ka->atlas;
+  c.atlas_mask = uint32_t(ka->atlas_size) - 1u;
+  c.atlas_fs = float(ka->atlas_size);
+  c.atlas_fts = float(ka->atlas_tex_size);
+}
+
 // TREE (colour-only): a glass primary hit's bounce tree by certified walks too (cert_tree; ltb and c.ax its
 // LDS slot), instead of leaving the whole pixel to the exact path.
 // us_out: the primary walk's certified prefix (CertResult::us) for the exact path, -1 if none.
 template <bool TEX = false, bool TREE = false, int NL = kWgThreads, bool LEAN = false>
-__device__ __forceinline__ bool cert_pixel(const Ctx& c, const Ray& ray0, f3& color_out, int max_refl = 0,
+__device__ __forceinline__ bool cert_pixel(const Ctx& c0, const Ray& ray0, f3& color_out, int max_refl = 0,
                                            int max_transp = 0, float* __restrict__ ltb = nullptr,
                                            float* us_out = nullptr) {
   const f3 P = ray0.pos, D = ray0.dir;
   if (!fast_path_ok(D)) { CERT_DIAG(0); return false; }
   int cx, cy, cz;
-  if (!exact_start_cell(c, P, D, cx, cy, cz) || !start_layers_clear<false>(c, P, D, cx, cy, cz, 0u)) {
+  if (!exact_start_cell(c0, P, D, cx, cy, cz) || !start_layers_clear<false>(c0, P, D, cx, cy, cz, 0u)) {
     CERT_DIAG(0);
     return false;
   }
   // hardware reciprocals (<= 1 ulp): the certified walk only needs its own error bounded
   const f3 rcp = mk(__builtin_amdgcn_rcpf(D.x), __builtin_amdgcn_rcpf(D.y), __builtin_amdgcn_rcpf(D.z));
-  CertResult h = cert_walk<false, LEAN, false>(c, P, D, rcp, c.max_len - ray0.len, cx, cy, cz, 0.0f,
+  CertResult h = cert_walk<false, LEAN, false>(c0, P, D, rcp, c0.max_len - ray0.len, cx, cy, cz, 0.0f,
                                                mk(0.0f, 0.0f, 0.0f), 0.0f, 0u);
   if (us_out) *us_out = h.us;
   CERT_DIAG_ONLY(cert_diag_iters(10, h.iters);)
+  if (LEAN && (PHASE_STOP(2) || PHASE_STOP(3))) {  // phase budget: the primary walk's result as the colour
+    color_out = mk(h.u, h.eu, float(h.cx + h.cy + h.cz + h.axis + int(h.byte) + h.res));
+    return true;
+  }
   if (h.res == CERT_UNSURE) { CERT_DIAG(1); return false; }
+  Ctx c = c0;  // LEAN: with the sun, the sky and the atlas read here (late_ctx)
+  if constexpr (LEAN) late_ctx(c);
   f3 color = mk(0.0f, 0.0f, 0.0f);
   if (h.res == CERT_MISS) {
     CERT_DIAG(2);
-    apply_sky_color(c, ray0, color);
+    if (!(LEAN && PHASE_STOP(6))) apply_sky_color(c, ray0, color);
     color_out = color;
     return true;
   }

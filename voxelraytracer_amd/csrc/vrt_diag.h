@@ -1,5 +1,5 @@
-// vrt_diag.h — the three diagnostic instruments of `make variant` builds (VRT_STAMPS, VRT_CERT_DIAG,
-// VRT_CERT_TRACE): their device globals, the one-line hooks the kernels call (all empty in the
+// vrt_diag.h — the diagnostic instruments of `make variant` builds (VRT_STAMPS, VRT_CERT_DIAG,
+// VRT_CERT_TRACE, and the phase cuts of VRT_PHASE_STOP): their device globals, the one-line hooks the kernels call (all empty in the
 // product library; images and counters unchanged) and their debug exports. Includes vrt_internal.h only.
 #ifndef VRT_DIAG_H
 #define VRT_DIAG_H
@@ -8,6 +8,21 @@
 
 #if (defined(VRT_STAMPS) || defined(VRT_CERT_DIAG) || defined(VRT_CERT_TRACE)) && !defined(VRT_DIAGNOSTIC_BUILD)
 #error "VRT_STAMPS / VRT_CERT_DIAG / VRT_CERT_TRACE are diagnostic builds: use make variant"
+#endif
+
+// ---- VRT_PHASE_STOP=k (make variant NAME=ph<k> DEFS=-DVRT_PHASE_STOP=<k>): the certified pass cut
+// short after phase k, for its per-phase instruction budget as PMC differences of consecutive builds
+// (DESIGN.md §6). What a phase computed goes into the pixel's colour, so it is not dead code; images
+// are meaningless. 0 launch and epilogue only, 1 + ray set-up, 2 + the primary walk's start checks and
+// prologue, 3 + its loop, 4 + lit term, shadow start and the shadow walk's prologue (and the sky of
+// primary misses), 5 + the shadow loop; the full build adds the colour. 6: the full pass without the sky.
+#ifdef VRT_PHASE_STOP
+#ifndef VRT_DIAGNOSTIC_BUILD
+#error "VRT_PHASE_STOP is a diagnostic build: use make variant"
+#endif
+#define PHASE_STOP(k) (VRT_PHASE_STOP == (k))
+#else
+#define PHASE_STOP(k) false
 #endif
 
 namespace vrt {

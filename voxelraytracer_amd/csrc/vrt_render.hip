@@ -164,7 +164,9 @@ __device__ __forceinline__ FrameView frame_view(const KArgs& a, uint32_t f) {
   return FrameView{b.inv_pv, b.time, b.cur, b.raw};
 }
 
-// Per-launch constants of the walk context
+// Per-launch constants of the walk context. LATE (the certified pass): without the sun, the sky
+// factor and the atlas, which cert_pixel reads after the primary walk (late_ctx, vrt_cert.h)
+template <bool LATE = false>
 __device__ __forceinline__ void init_ctx(Ctx& c, const KArgs& a, const uint16_t* __restrict__ vox) {
   c.vox = vox;
   c.ostride = a.ostride;
@@ -172,16 +174,24 @@ __device__ __forceinline__ void init_ctx(Ctx& c, const KArgs& a, const uint16_t*
   c.p = uint32_t(a.n) + 1u;
   c.fn = a.fn;
   c.max_len = a.max_len;
-  c.sky_sy = a.sky_sy;
-  c.sun_n = mk(a.sun_n[0], a.sun_n[1], a.sun_n[2]);
-  c.sun_rcp = mk(a.sun_rcp[0], a.sun_rcp[1], a.sun_rcp[2]);
   c.time = a.time;
   c.refl_noise = a.refl_noise;
   c.refr_noise = a.refr_noise;
-  c.atlas = a.atlas;
-  c.atlas_mask = uint32_t(a.atlas_size) - 1u;
-  c.atlas_fs = float(a.atlas_size);
-  c.atlas_fts = float(a.atlas_tex_size);
+  if constexpr (LATE) {
+    c.sky_sy = 0.0f;
+    c.sun_n = c.sun_rcp = mk(0.0f, 0.0f, 0.0f);
+    c.atlas = nullptr;
+    c.atlas_mask = 0u;
+    c.atlas_fs = c.atlas_fts = 0.0f;
+  } else {
+    c.sky_sy = a.sky_sy;
+    c.sun_n = mk(a.sun_n[0], a.sun_n[1], a.sun_n[2]);
+    c.sun_rcp = mk(a.sun_rcp[0], a.sun_rcp[1], a.sun_rcp[2]);
+    c.atlas = a.atlas;
+    c.atlas_mask = uint32_t(a.atlas_size) - 1u;
+    c.atlas_fs = float(a.atlas_size);
+    c.atlas_fts = float(a.atlas_tex_size);
+  }
   CTRACE_ONLY(c.tr = false;)
 }
 
@@ -379,7 +389,8 @@ __device__ __forceinline__ bool exact_pixel(const KArgs& a, const Ctx& c, Ray ra
 
 // output of one pixel: float RGBA, or the fused reference post-pass (RGB8 ray-trace store,
 // temporal blend, RGB8 store)
-__device__ __forceinline__ void store_pixel(const KArgs& a, const FrameView& fv, float4* __restrict__ out,
+template <class KA>  // KArgs, or the certified pass's late view of them (LateKArgs)
+__device__ __forceinline__ void store_pixel(const KA& a, const FrameView& fv, float4* __restrict__ out,
                                             size_t o, const f3 color) {
   if (fv.cur) {
     const uint32_t rw = pack_rgb8(color.x, color.y, color.z);
@@ -456,7 +467,7 @@ __global__ void __launch_bounds__(kWgThreads, TREE ? kTreeWaves : (DEFER ? kDefe
 
   if (valid) {
     Ctx c;
-    init_ctx(c, a, vox);
+    init_ctx<DEFER>(c, a, vox);
     CTRACE_ONLY(c.tr = px == VRT_TRACE_PX && frame_row(a, li) == VRT_TRACE_PY;)
     if constexpr (FB) c.time = frame_view(a, fr).time;
     // one LDS pool: the exact path's axis table and bounce-stack bottom (in-lane instances), and
@@ -486,7 +497,13 @@ __global__ void __launch_bounds__(kWgThreads, TREE ? kTreeWaves : (DEFER ? kDefe
       tstk = reinterpret_cast<float*>(lds_pool) + kAxFloats + threadIdx.x;   // (and c.ax: tree_put)
     }
     float us = -1.0f;  // the primary walk's certified prefix, for the exact path
-    const bool need_exact = CERT < 2 || !cert_pixel<TEX, TREE, kWgThreads, DEFER>(c, ray, color, a.max_refl, a.max_transp, tstk, &us);
+    bool need_exact;
+    if (DEFER && (PHASE_STOP(0) || PHASE_STOP(1))) {  // phase budget: nothing, or the ray alone, as the colour
+      if (PHASE_STOP(1)) color = mk(ray.pos.x + ray.dir.x, ray.pos.y + ray.dir.y, ray.pos.z + ray.dir.z);
+      need_exact = false;
+    } else {
+      need_exact = CERT < 2 || !cert_pixel<TEX, TREE, kWgThreads, DEFER>(c, ray, color, a.max_refl, a.max_transp, tstk, &us);
+    }
     STAMP_WAVE_CERT(need_exact);
     if constexpr (DEFER) {
       deferred = need_exact;
@@ -509,7 +526,21 @@ __global__ void __launch_bounds__(kWgThreads, TREE ? kTreeWaves : (DEFER ? kDefe
     }
     // the frame's outputs read here, where they are used (kept live across the walks they were
     // held in registers, and their spills cost the in-lane exact instance 4 %)
-    if (!deferred) store_pixel(a, FB ? frame_view(a, fr) : FrameView{a.inv_pv, a.time, a.cur, a.raw}, out, o, color);
+    if constexpr (DEFER) {
+      // (the certified pass: through the opaque view of the arguments; the compiler had moved the
+      // plain reads above both walks all the same, six SGPRs)
+      if (!deferred) {
+        LateKArgs* ka = late_kargs();
+        uint32_t *cur = ka->cur, *raw = ka->raw;
+        if (FB && fr != 0u) {
+          cur = ka->fb[fr - 1u].cur;
+          raw = ka->fb[fr - 1u].raw;
+        }
+        store_pixel(*ka, FrameView{nullptr, 0.0f, cur, raw}, out, o, color);
+      }
+    } else {
+      if (!deferred) store_pixel(a, FB ? frame_view(a, fr) : FrameView{a.inv_pv, a.time, a.cur, a.raw}, out, o, color);
+    }
   }
   if constexpr (DEFER) {  // the wave's deferred pixels to the exact pass's list: ballot compaction
     const unsigned long long m = __ballot(deferred);
@@ -711,10 +742,11 @@ void launch_render(const KArgs& a, bool stats, const uint16_t* vox, float4* out,
                                       : exact_pass_kernel<false, 2, kFatWaves, kSparseBatchFat>)
                                 : (fb ? exact_pass_kernel<false, 2, kExactWaves, kSparseBatch, true>
                                       : exact_pass_kernel<false, 2>));
+    const uint32_t pad = a.tree ? 0u : kDeferLdsPad;  // (an occupancy A/B knob, vrt_tuning.h)
     if (ev_begin)
-      hipExtLaunchKernelGGL(k1, g1, dim3(kWgThreads), 0, s, ev_begin, nullptr, 0, a, vox, out, hit, cnt_rep);
+      hipExtLaunchKernelGGL(k1, g1, dim3(kWgThreads), pad, s, ev_begin, nullptr, 0, a, vox, out, hit, cnt_rep);
     else
-      hipLaunchKernelGGL(k1, g1, dim3(kWgThreads), 0, s, a, vox, out, hit, cnt_rep);
+      hipLaunchKernelGGL(k1, g1, dim3(kWgThreads), pad, s, a, vox, out, hit, cnt_rep);
     if (ev_end)
       hipExtLaunchKernelGGL(k2, g2, dim3(64), 0, s, nullptr, ev_end, 0, a, vox, out);
     else

@@ -13,7 +13,7 @@
      defined(VRT_SPARSE_BATCH_FAT) || defined(VRT_EXACT_PRIO) || defined(VRT_FWD_CAP) || defined(VRT_WG_WAVES) || \
      defined(VRT_ORD_DIV) || defined(VRT_ORD_MIN_ROUNDS) || defined(VRT_DEFER_GRID_DIV) ||                      \
      defined(VRT_DEFER_GRID_DIV_COLOR) || defined(VRT_QUERY_WG_WAVES) || defined(VRT_TRACE_WG_WAVES) ||         \
-     defined(VRT_TRACE_MIN_WAVES)) &&                                                                         \
+     defined(VRT_TRACE_MIN_WAVES) || defined(VRT_DEFER_LDS_PAD)) &&                                                                         \
     !defined(VRT_DIAGNOSTIC_BUILD)
 #error "the VRT_* tuning values are A/B knobs of make variant builds (make variant NAME=... DEFS=-DVRT_...=...)"
 #endif
@@ -26,6 +26,9 @@
 #endif
 #ifndef VRT_DEFER_WAVES
 #define VRT_DEFER_WAVES 7
+#endif
+#ifndef VRT_DEFER_LDS_PAD
+#define VRT_DEFER_LDS_PAD 0
 #endif
 #ifndef VRT_EXACT_WAVES
 #define VRT_EXACT_WAVES VRT_MIN_WAVES
@@ -93,8 +96,17 @@ constexpr int kMinWaves = VRT_MIN_WAVES;
 // spilled VGPRs, 8 bytes of scratch and 74-140 SGPR spills against 16-58, and run slower,
 // alternating with the 7-wave library, ms per frame 7 -> 8: C3 0.0346 / 0.0346 / 0.0348 -> 0.0358 /
 // 0.0362 / 0.0358, C2 0.0530 / 0.0529 -> 0.0550 / 0.0548, C4 0.1210 / 0.1209 -> 0.1300 / 0.1305, C1
-// 0.1207 / 0.1205 -> 0.1204 / 0.1205 (profiles/r08_walk/ab_bench.txt). 7 stays.
+// 0.1207 / 0.1205 -> 0.1204 / 0.1205 (profiles/r08_walk/ab_bench.txt). 7 stays: as the floor the
+// instances are built for. Since r09 (cert_walk's result no longer carried through its loop) the
+// DEFER instances without trees take 56 VGPRs, spill nothing and run 8 to a SIMD, which is now the
+// faster state: capped at 7 by kDeferLdsPad below, C3 0.0332 / 0.0334 / 0.0333 -> 0.0344 / 0.0345 /
+// 0.0343 ms per frame (profiles/r09_exit/ab_occupancy.txt).
 constexpr int kDeferWaves = VRT_DEFER_WAVES;
+// Dynamic LDS bytes per workgroup of the certified pass without trees (launch_render): an occupancy
+// cap for A/B builds. kDeferWaves is a floor: since the one-exit walk loop (r09) the DEFER instances
+// take 56 VGPRs and the hardware runs them 8 waves to a SIMD. 11264 bytes let 14 two-wave workgroups
+// share a CU's 160 KiB: 7 waves per SIMD.
+constexpr uint32_t kDeferLdsPad = VRT_DEFER_LDS_PAD;
 // resident waves per SIMD of the exact pass's whole-frame instance (see exact_pass_kernel, WAVES)
 constexpr int kExactWaves = VRT_EXACT_WAVES;
 // resident waves per SIMD of the certified pass with certified trees
