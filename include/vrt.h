@@ -25,8 +25,9 @@
  *     is one launch, and up to four frames are in flight (ABI v9). The *_async band entry points
  *     run on the context's first (root) device, as do the ray queries (vrt_cast_rays*,
  *     vrt_pick_pixels: which voxel a ray meets), the shaded ray queries (vrt_trace_rays*,
- *     vrt_trace_pixels: which colour a ray sees) and the ID and depth pass (vrt_render_ids*: which
- *     voxel and face every pixel shows, and how far away).
+ *     vrt_trace_pixels: which colour a ray sees), the ID and depth pass (vrt_render_ids*: which
+ *     voxel and face every pixel shows, and how far away) and the reprojected temporal filter
+ *     (vrt_reproject_temporal_async, vrt_render_frame_reprojected: a history that follows the camera).
  */
 #ifndef VRT_H
 #define VRT_H
@@ -230,7 +231,8 @@ int vrt_certified(const vrt_ctx* ctx);
 
 /* ABI v8 (r02): device timestamps of the async band launches (vrt_render_rows*_async,
  * vrt_render_temporal_rows*_async on the first device) and of the ray-query launches (vrt_cast_rays*,
- * vrt_pick_pixels, vrt_trace_rays*, vrt_trace_pixels, vrt_render_ids*: one launch per call):
+ * vrt_pick_pixels, vrt_trace_rays*, vrt_trace_pixels, vrt_render_ids*, vrt_reproject_temporal_async: one
+ * launch per call):
  * vrt_set_launch_timing(ctx, n) creates
  * timing events for the next n launches (0: off; it synchronises the first device when replacing
  * earlier events), each launch then records its kernel's start and end on the device
@@ -509,6 +511,69 @@ int vrt_render_ids(vrt_ctx* ctx, const vrt_camera* cam, const vrt_params* params
  * call. */
 int vrt_ids_deferred(vrt_ctx* ctx, uint64_t* pixels, uint64_t* deferred);
 
+/* ---- reprojected temporal filter (added within v15: detect by symbol lookup) ----------------- */
+/* A temporal filter whose history follows the camera: the first consumer of the ID and depth pass. The
+ * reference's filter (temporal.glsl:18, vrt_render_frame) blends a pixel with the same pixel of the previous
+ * filtered frame, which is right only while the camera stands still. Here each pixel's history is fetched
+ * where its surface point was on screen in the previous frame, and it is used only if the previous frame
+ * showed the same face of the same voxel with the same material byte there: both words of the two
+ * vrt_pixel_id records equal, no depth or normal threshold. An edited voxel drops its history by
+ * construction (DESIGN.md §6 "Reprojected temporal filter"). */
+
+/* The filter over rows [row0, row0 + rows) of the current frame, one kernel launch on hip_stream (one
+ * launch for vrt_set_launch_timing), on the context's first device: no memset, no allocation, no atomics, no
+ * context-owned state, capturable like vrt_render_ids_async.
+ *   d_raw_rgba8, d_ids, d_depth, d_out_rgba8, d_src (optional): band-indexed, pixel (px, row0 + i) at
+ *     [i * pitch + px], as vrt_render_ids_async writes d_ids and d_depth. d_raw_rgba8 is the quantised
+ *     ray-traced frame (RGBA8 words, e.g. vrt_render_temporal_rows_async at u_Alpha = 1).
+ *   d_prev_rgba8, d_prev_ids: the WHOLE previous filtered frame and its ID records, width x height with
+ *     prev_pitch >= width pixels between rows; both NULL: no history.
+ *   cam, params: those d_ids and d_depth were rendered with (only the fields the pick reads are read);
+ *     prev_pv: the previous frame's forward matrix (vrt_camera_forward of its camera).
+ * Per pixel, in float32 and in exactly this order (no contraction, correctly rounded division):
+ *   1. pos, dir: the pixel's primary ray, as vrt_render_ids_async forms it (depth is measured along it);
+ *   2. a hit (voxel_index >= 0): v[i] = (pos[i] + depth * dir[i]) - float(N) * 0.5f, w = 1;
+ *      a miss: v = dir, w = 0 (the sky is a point at infinity);
+ *   3. clip[r] = ((m[0*4+r] * v.x + m[1*4+r] * v.y) + m[2*4+r] * v.z) + m[3*4+r] * w, m = prev_pv;
+ *   4. !(clip[3] > 0): code -2 (behind the previous camera, or NaN);
+ *   5. sx = ((clip[0] / clip[3]) * 0.5f + 0.5f) * float(width), sy likewise from clip[1] and height;
+ *   6. !(sx >= 0 && sx < width && sy >= 0 && sy < height), on the floats: code -1;
+ *   7. qx = int(floorf(sx)), qy = int(floorf(sy)): a nearest fetch;
+ *   8. either word of d_prev_ids[qy * prev_pitch + qx] differs from the pixel's d_ids record: code -3;
+ *   9. else accepted: src = qy * width + qx.
+ * Accepted pixels get temporal.glsl's blend of the raw pixel with d_prev_rgba8[qy * prev_pitch + qx] at
+ * alpha (the frame kernels' own blend on RGB8 texels), every other pixel the raw pixel. d_src receives src
+ * or the code; -4 = no history (precedence -4, -2, -1, -3).
+ * The output must not alias the previous frame (the kernel reads other pixels' history).
+ * VRT_ERR_NO_VOLUME without a resident volume; VRT_ERR_INVALID for a null cam, params, prev_pv, d_raw_rgba8,
+ * d_ids, d_depth or d_out_rgba8, a bad image size, rows < 0 or a band outside the image, pitch or prev_pitch
+ * < width, exactly one of d_prev_rgba8 and d_prev_ids NULL, d_out_rgba8 == d_prev_rgba8, an ID buffer not
+ * 8-byte or another buffer not 4-byte aligned. rows == 0 is a successful no-op. A failed call writes nothing. */
+int vrt_reproject_temporal_async(vrt_ctx* ctx, const vrt_camera* cam, const vrt_params* params,
+                                 const float prev_pv[16], float alpha, int32_t row0, int32_t rows, int32_t pitch,
+                                 const uint32_t* d_raw_rgba8, const vrt_pixel_id* d_ids, const float* d_depth,
+                                 const uint32_t* d_prev_rgba8, const vrt_pixel_id* d_prev_ids, int32_t prev_pitch,
+                                 uint32_t* d_out_rgba8, int32_t* d_src, void* hip_stream);
+
+/* The synchronous frame loop with that filter: like vrt_render_frame, with a history of its own in the
+ * context (ping-pong filtered frames and ID buffers, the previous camera's forward matrix, staging that
+ * grows on demand; vrt_render_frame's history is not touched). Each call, on a context stream of the first
+ * device (multi-device contexts run all of it there, like the ID pass): the quantised ray-traced frame of
+ * (cam, params); the ID and depth pass of (cam, params with ray_noise = 0): geometry buffers are noise-free,
+ * since a noised primary ray's hit belongs at another screen position; the filter with those noise-free
+ * params against the previous call's output, IDs and matrix; the copy to out_rgba8 (W*H*4 bytes).
+ * The first call has no history, so its output is the raw frame, as is the first after a change of the image
+ * size, after vrt_reprojected_history_reset, or after a frame whose camera matrix has no inverse.
+ * stats (optional): kernel_ms is the GPU time from the first launch's start to the last launch's end;
+ * counters (VRT_STATS_COUNTERS) are VRT_ERR_UNSUPPORTED.
+ * Limits: the fetch is nearest, so a history that is resampled frame after frame drifts by up to half a
+ * pixel per frame; the exact ID pass runs inside every call. */
+int vrt_render_frame_reprojected(vrt_ctx* ctx, const vrt_camera* cam, const vrt_params* params, float alpha,
+                                 uint8_t* out_rgba8, vrt_stats* stats);
+
+/* The next vrt_render_frame_reprojected has no history: its output is its raw frame. */
+int vrt_reprojected_history_reset(vrt_ctx* ctx);
+
 /* ---- textured mode (voxel.glsl without _COLOR_ONLY) --------------------- */
 /* With vrt_params.color_only = 0 the kernel shades with the textured material table
  * (voxel.glsl:51-68) and GetColor reads the atlas (:174-182) at GetTextureCoordinate (:167-172)
@@ -654,6 +719,12 @@ int vrt_build_scene(int32_t scene, int32_t n, uint32_t seed, uint8_t* out);
  * degrees. Computed in double, rounded to float. */
 int vrt_camera_make(const float pos[3], const float rot_deg[3], int32_t width, int32_t height,
                     float fov_deg, float near_plane, float far_plane, vrt_camera* out);
+
+/* Added within v15. PV = inverse(cam->inv_pv), column-major like inv_pv: the forward matrix that takes a
+ * world point to the camera's clip coordinates (vrt_reproject_temporal_async's prev_pv). Computed in
+ * double and rounded to float, as vrt_camera_make computes its inverse. Host arithmetic, no GPU.
+ * VRT_ERR_INVALID for null pointers and for a singular (or non-finite) matrix. */
+int vrt_camera_forward(const vrt_camera* cam, float out_pv[16]);
 
 /* u_SunDir from the day/night clock (main.cpp:346-348). */
 void vrt_sun_dir(float time_of_day, float day_time, float out[3]);

@@ -69,6 +69,16 @@ def make_camera(width: int, height: int, pos=DEFAULT_CAM_POS, rot=DEFAULT_CAM_RO
     return cam
 
 
+def camera_forward(cam: Camera) -> np.ndarray:
+    """vrt_camera_forward: PV = inverse(cam.inv_pv) as 16 float32, column-major like inv_pv: the matrix that
+    takes a world point to the camera's clip coordinates (Renderer.reproject_temporal_async's prev_pv)."""
+    out = np.zeros(16, dtype=np.float32)
+    rc = lib().vrt_camera_forward(C.byref(cam), out.ctypes.data)
+    if rc != 0:
+        raise VrtError(rc, "vrt_camera_forward")
+    return out
+
+
 def sun_dir(time_of_day: float, day_time: float = 50.0):
     out = (C.c_float * 3)()
     lib().vrt_sun_dir(time_of_day, day_time, C.byref(out))
@@ -463,6 +473,39 @@ class Renderer:
         px, de = C.c_uint64(), C.c_uint64()
         self._check(self._lib.vrt_ids_deferred(self._h, C.byref(px), C.byref(de)), "vrt_ids_deferred")
         return int(px.value), int(de.value)
+
+    def reproject_temporal_async(self, cam: Camera, params: Params, prev_pv, alpha: float, row0: int, rows: int,
+                                 pitch: int, d_raw: int, d_ids: int, d_depth: int, d_prev: int, d_prev_ids: int,
+                                 prev_pitch: int, d_out: int, d_src: int = 0, stream: int = 0):
+        """vrt_reproject_temporal_async: the reprojected temporal filter over rows [row0, row0 + rows), one
+        kernel launch enqueued on a HIP stream. Device pointers (e.g. torch tensors' data_ptr()): d_raw,
+        d_ids, d_depth, d_out and d_src (0: none) are band-indexed with `pitch` pixels per row, as
+        render_ids_async writes them; d_prev and d_prev_ids are the whole previous frame and its IDs with
+        prev_pitch pixels per row (both 0: no history). prev_pv: camera_forward() of the previous camera.
+        d_src receives, per pixel, the previous frame's pixel index the history came from, or -1 (outside
+        the previous image), -2 (behind the previous camera), -3 (another voxel, face or material there),
+        -4 (no history)."""
+        pv = np.ascontiguousarray(prev_pv, dtype=np.float32).reshape(16)
+        self._check(self._lib.vrt_reproject_temporal_async(
+            self._h, C.byref(cam), C.byref(params), pv.ctypes.data, alpha, row0, rows, pitch, d_raw or None,
+            d_ids or None, d_depth or None, d_prev or None, d_prev_ids or None, prev_pitch, d_out or None,
+            d_src or None, stream or None), "vrt_reproject_temporal_async")
+
+    def render_frame_reprojected(self, cam: Camera, params: Params, alpha: float, timing: bool = False):
+        """vrt_render_frame_reprojected: the frame loop with the reprojected temporal filter and a history of
+        its own in the context (render_frame's is not touched). Returns the filtered frame rgba8[H, W, 4]
+        uint8, or (frame, kernel_ms) with timing=True. The first call, the first after a change of the image
+        size and the first after reprojected_history_reset() return the raw frame."""
+        out = np.empty((cam.height, cam.width, 4), dtype=np.uint8)
+        st = abi.Stats() if timing else None
+        self._check(self._lib.vrt_render_frame_reprojected(self._h, C.byref(cam), C.byref(params), alpha,
+                                                           out.ctypes.data, C.byref(st) if timing else None),
+                    "vrt_render_frame_reprojected")
+        return (out, float(st.kernel_ms)) if timing else out
+
+    def reprojected_history_reset(self):
+        """vrt_reprojected_history_reset: the next render_frame_reprojected has no history."""
+        self._check(self._lib.vrt_reprojected_history_reset(self._h), "vrt_reprojected_history_reset")
 
     def debug_packed_volume(self) -> np.ndarray:
         """The kernel's device volumes [octant][z][y][x] ((N+1)^3 u16 voxel | G << 8 each; 8

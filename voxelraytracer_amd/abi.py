@@ -159,7 +159,10 @@ ADDED_IN = {"vrt_render_temporal_batch_async": 14, "vrt_set_cert_trees": 15,
             # added within v15 after the ray queries (shaded ray queries)
             "vrt_trace_rays_async": 16, "vrt_trace_rays": 16, "vrt_trace_pixels": 16,
             # added within v15 after the shaded ray queries (ID and depth pass)
-            "vrt_render_ids_async": 16, "vrt_render_ids": 16, "vrt_ids_deferred": 16}
+            "vrt_render_ids_async": 16, "vrt_render_ids": 16, "vrt_ids_deferred": 16,
+            # added within v15 after the ID and depth pass (reprojected temporal filter)
+            "vrt_camera_forward": 16, "vrt_reproject_temporal_async": 16, "vrt_render_frame_reprojected": 16,
+            "vrt_reprojected_history_reset": 16}
 
 SIGNATURES = {
     "vrt_abi_version": (C.c_int, []),
@@ -209,6 +212,15 @@ SIGNATURES = {
                                        C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vrt_render_ids": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.c_void_p, C.c_void_p]),
     "vrt_ids_deferred": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    # added within v15 (detect by symbol lookup): reprojected temporal filter
+    "vrt_camera_forward": (C.c_int, [C.POINTER(Camera), C.c_void_p]),
+    "vrt_reproject_temporal_async": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.c_void_p,
+                                               C.c_float, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                               C.c_void_p, C.c_void_p]),
+    "vrt_render_frame_reprojected": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.c_float,
+                                               C.c_void_p, C.POINTER(Stats)]),
+    "vrt_reprojected_history_reset": (C.c_int, [C.c_void_p]),
     "vrt_build_scene_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p]),
     "vrt_debug_packed_volume": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
     "vrt_debug_collectives": (C.c_int, [C.c_void_p]),

@@ -178,6 +178,20 @@ struct vrt_ctx {
   float* d_depth_stage = nullptr;
   size_t ids_stage_px = 0;
   uint64_t ids_pixels = 0, ids_deferred = 0;
+  // first device: vrt_render_frame_reprojected's staging for frames of rp_w x rp_h (rp_px pixels allocated):
+  // the raw frame, the depth, ping-pong filtered frames and noise-free ID buffers (rp_cur: the last call's),
+  // the last call's forward matrix, and whether the next call has a history (rp_valid). Separate from
+  // vrt_render_frame's ring. ev_rp_beg / ev_rp_end: device timestamps of a call's first and last launch
+  uint32_t* d_rp_raw = nullptr;
+  float* d_rp_depth = nullptr;
+  uint32_t* d_rp_out[2] = {};
+  vrt_pixel_id* d_rp_ids[2] = {};
+  size_t rp_px = 0;
+  int32_t rp_w = 0, rp_h = 0;
+  int rp_cur = 0;
+  bool rp_valid = false;
+  float rp_pv[16] = {};
+  hipEvent_t ev_rp_beg = nullptr, ev_rp_end = nullptr;
   // ABI v12: this process's rank of a one-process-per-GPU job (vrt_comm_join): one RCCL
   // communicator per lane, so that frames in flight on different lane streams gather without
   // ordering each other (a communicator's operations run in issue order)
@@ -1242,6 +1256,11 @@ void vrt_destroy(vrt_ctx* c) {
     if (c->d_query_out) (void)hipFree(c->d_query_out);
     if (c->d_ids_stage) (void)hipFree(c->d_ids_stage);
     if (c->d_depth_stage) (void)hipFree(c->d_depth_stage);
+    for (void* b : {(void*)c->d_rp_raw, (void*)c->d_rp_depth, (void*)c->d_rp_out[0], (void*)c->d_rp_out[1],
+                    (void*)c->d_rp_ids[0], (void*)c->d_rp_ids[1]})
+      if (b) (void)hipFree(b);
+    if (c->ev_rp_beg) (void)hipEventDestroy(c->ev_rp_beg);
+    if (c->ev_rp_end) (void)hipEventDestroy(c->ev_rp_end);
     if (!c->lt_ev.empty()) (void)hipDeviceSynchronize();
     for (hipEvent_t e : c->lt_ev) (void)hipEventDestroy(e);
   }
@@ -1817,6 +1836,160 @@ int vrt_ids_deferred(vrt_ctx* ctx, uint64_t* pixels, uint64_t* deferred) {
   if (!pixels || !deferred) return fail(ctx, VRT_ERR_INVALID, "null output");
   *pixels = ctx->ids_pixels;
   *deferred = ctx->ids_deferred;
+  return VRT_OK;
+}
+
+// ---- reprojected temporal filter (vrt_reproject_kernels.h) --------------------------------------
+
+// What vrt_reproject_temporal_async checks beyond check_ids (which takes the band's ids and depth)
+static int check_reproject(vrt_ctx* ctx, const vrt_camera* cam, const float* prev_pv, int32_t prev_pitch,
+                           const void* raw, const void* depth, const void* prev, const void* prev_ids, const void* out,
+                           const void* src) {
+  if (!prev_pv) return fail(ctx, VRT_ERR_INVALID, "null previous matrix");
+  if (!raw || !depth || !out) return fail(ctx, VRT_ERR_INVALID, "null raw, depth or output buffer");
+  if (prev_pitch < cam->width) return fail(ctx, VRT_ERR_INVALID, "previous row pitch must be >= the image width");
+  if ((prev == nullptr) != (prev_ids == nullptr))
+    return fail(ctx, VRT_ERR_INVALID, "the previous frame and its id buffer are given together or not at all");
+  if (prev && out == prev) return fail(ctx, VRT_ERR_INVALID, "the output must not alias the previous frame");
+  const uintptr_t words = reinterpret_cast<uintptr_t>(raw) | reinterpret_cast<uintptr_t>(prev) |
+                          reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(src);
+  if ((words & 3u) != 0 || (reinterpret_cast<uintptr_t>(prev_ids) & 7u) != 0)
+    return fail(ctx, VRT_ERR_INVALID, "device id buffers must be 8-byte aligned, the other buffers 4-byte aligned");
+  return VRT_OK;
+}
+
+// One reprojection launch over rows [row0, row0 + rows) (rows >= 1) on `st`: no allocation, no host
+// synchronisation. eb / ee: the launch's device timestamps (optional)
+static int enqueue_reproject(vrt_ctx* ctx, const vrt_camera* cam, const vrt_params* p, const float* prev_pv, float alpha,
+                             int32_t row0, int32_t rows, int32_t pitch, const uint32_t* d_raw, const vrt_pixel_id* d_ids,
+                             const float* d_depth, const uint32_t* d_prev, const vrt_pixel_id* d_prev_ids,
+                             int32_t prev_pitch, uint32_t* d_out, int32_t* d_src, hipStream_t st, hipEvent_t eb,
+                             hipEvent_t ee) {
+  Shard& s = ctx->sh[0];
+  // the frame's argument block, as enqueue_ids fills it: primary_ray reads it
+  vrt::KArgs a = make_args(ctx, s, cam, p, row0, rows, 1);
+  a.vdiv_ok = vertex_div_ranges_ok(a.inv_pv) ? 1u : 0u;
+  a.pitch = pitch;
+  vrt::ReprojArgs r;
+  std::memcpy(r.pv, prev_pv, sizeof(r.pv));
+  r.alpha = alpha;
+  r.prev_pitch = prev_pitch;
+  r.raw = d_raw;
+  r.ids = reinterpret_cast<const uint2*>(d_ids);
+  r.depth = d_depth;
+  r.prev = d_prev;
+  r.prev_ids = reinterpret_cast<const uint2*>(d_prev_ids);
+  r.out = d_out;
+  r.src = d_src;
+  vrt::launch_reproject(a, r, st, eb, ee);
+  VRT_HIP(ctx, hipGetLastError());
+  return VRT_OK;
+}
+
+int vrt_reproject_temporal_async(vrt_ctx* ctx, const vrt_camera* cam, const vrt_params* p, const float prev_pv[16],
+                                 float alpha, int32_t row0, int32_t rows, int32_t pitch, const uint32_t* d_raw_rgba8,
+                                 const vrt_pixel_id* d_ids, const float* d_depth, const uint32_t* d_prev_rgba8,
+                                 const vrt_pixel_id* d_prev_ids, int32_t prev_pitch, uint32_t* d_out_rgba8,
+                                 int32_t* d_src, void* hip_stream) {
+  if (!ctx) return VRT_ERR_INVALID;
+  int st = check_ids(ctx, cam, p, row0, rows, pitch, d_ids, d_depth, true);
+  if (st != VRT_OK) return st;
+  st = check_reproject(ctx, cam, prev_pv, prev_pitch, d_raw_rgba8, d_depth, d_prev_rgba8, d_prev_ids, d_out_rgba8,
+                       d_src);
+  if (st != VRT_OK || rows == 0) return st;
+  hipEvent_t eb, ee;
+  launch_timing_events(ctx, eb, ee);
+  return enqueue_reproject(ctx, cam, p, prev_pv, alpha, row0, rows, pitch, d_raw_rgba8, d_ids, d_depth, d_prev_rgba8,
+                           d_prev_ids, prev_pitch, d_out_rgba8, d_src, static_cast<hipStream_t>(hip_stream), eb, ee);
+}
+
+// The staging of vrt_render_frame_reprojected on the first device (the current one), for frames of w x h:
+// the raw frame, the depth, and ping-pong filtered frames and ID buffers. Synchronous calls only, so no
+// launch still uses buffers that are replaced here. A new size drops the history.
+static int ensure_reproject_stage(vrt_ctx* ctx, int32_t w, int32_t h) {
+  if (w == ctx->rp_w && h == ctx->rp_h) return VRT_OK;
+  const size_t px = size_t(w) * size_t(h);
+  ctx->rp_w = ctx->rp_h = 0;
+  ctx->rp_valid = false;
+  if (ctx->rp_px < px) {
+    void** bufs[] = {(void**)&ctx->d_rp_raw, (void**)&ctx->d_rp_depth, (void**)&ctx->d_rp_out[0],
+                     (void**)&ctx->d_rp_out[1], (void**)&ctx->d_rp_ids[0], (void**)&ctx->d_rp_ids[1]};
+    const size_t elem[] = {4, 4, 4, 4, sizeof(vrt_pixel_id), sizeof(vrt_pixel_id)};
+    for (void** b : bufs) {
+      if (*b) (void)hipFree(*b);
+      *b = nullptr;
+    }
+    ctx->rp_px = 0;
+    for (int i = 0; i < 6; ++i)
+      if (hipMalloc(bufs[i], px * elem[i]) != hipSuccess) {
+        for (void** b : bufs) {
+          if (*b) (void)hipFree(*b);
+          *b = nullptr;
+        }
+        return fail(ctx, VRT_ERR_OOM, "hipMalloc reprojected-frame staging");
+      }
+    ctx->rp_px = px;
+  }
+  if (!ctx->ev_rp_beg) VRT_HIP(ctx, hipEventCreate(&ctx->ev_rp_beg));
+  if (!ctx->ev_rp_end) VRT_HIP(ctx, hipEventCreate(&ctx->ev_rp_end));
+  ctx->rp_w = w;
+  ctx->rp_h = h;
+  return VRT_OK;
+}
+
+int vrt_render_frame_reprojected(vrt_ctx* ctx, const vrt_camera* cam, const vrt_params* p, float alpha,
+                                 uint8_t* out_rgba8, vrt_stats* stats) {
+  if (!ctx) return VRT_ERR_INVALID;
+  int st = check_render_args(ctx, cam, p);
+  if (st != VRT_OK) return st;
+  if (!out_rgba8) return fail(ctx, VRT_ERR_INVALID, "null output");
+  if (stats && (stats->request & VRT_STATS_COUNTERS))
+    return fail(ctx, VRT_ERR_UNSUPPORTED, "vrt_render_frame_reprojected does not count");
+  DeviceGuard guard;
+  Shard& s = ctx->sh[0];
+  VRT_HIP(ctx, hipSetDevice(s.device));
+  const int32_t w = cam->width, h = cam->height;
+  if ((st = ensure_reproject_stage(ctx, w, h)) != VRT_OK) return st;
+  const size_t bytes = size_t(w) * size_t(h) * 4;
+  if ((st = ensure_stage(ctx, bytes)) != VRT_OK) return st;
+  hipStream_t ms = main_stream(s);
+  const int cur = ctx->rp_cur ^ 1, prev = ctx->rp_cur;
+  // 1. the quantised ray-traced frame: the temporal band path at u_Alpha = 1 (its output is the raw frame)
+  vrt::KArgs a = make_args(ctx, s, cam, p, 0, h, 1);
+  a.alpha = 1.0f;
+  a.prev = ctx->d_rp_raw;
+  a.cur = ctx->d_rp_raw;
+  launch(ctx, s, a, nullptr, nullptr, nullptr, ms, stats ? ctx->ev_rp_beg : nullptr, nullptr);
+  VRT_HIP(ctx, hipGetLastError());
+  // 2. noise-free geometry buffers: a noised primary ray's hit belongs at another screen position
+  vrt_params geom = *p;
+  geom.ray_noise = 0.0f;
+  if ((st = enqueue_ids(ctx, cam, &geom, 0, h, w, ctx->d_rp_ids[cur], ctx->d_rp_depth, ms)) != VRT_OK) return st;
+  // 3. the filter against the previous call's frame, IDs and matrix
+  const bool hist = ctx->rp_valid;
+  st = enqueue_reproject(ctx, cam, &geom, ctx->rp_pv, alpha, 0, h, w, ctx->d_rp_raw, ctx->d_rp_ids[cur], ctx->d_rp_depth,
+                         hist ? ctx->d_rp_out[prev] : nullptr, hist ? ctx->d_rp_ids[prev] : nullptr, w,
+                         ctx->d_rp_out[cur], nullptr, ms, nullptr, stats ? ctx->ev_rp_end : nullptr);
+  if (st != VRT_OK) return st;
+  // 4. to the host through the pinned staging
+  VRT_HIP(ctx, hipMemcpyAsync(ctx->h_stage, ctx->d_rp_out[cur], bytes, hipMemcpyDeviceToHost, ms));
+  VRT_HIP(ctx, hipStreamSynchronize(ms));
+  std::memcpy(out_rgba8, ctx->h_stage, bytes);
+  if (stats) {  // the span from the first launch's start to the last launch's end, as vrt_render_frame's
+    float ms_span = 0.0f;
+    VRT_HIP(ctx, hipEventElapsedTime(&ms_span, ctx->ev_rp_beg, ctx->ev_rp_end));
+    stats->kernel_ms = ms_span;
+  }
+  // this frame is the next call's history, if its camera has a forward matrix
+  ctx->rp_cur = cur;
+  ctx->rp_valid = vrt_camera_forward(cam, ctx->rp_pv) == VRT_OK;
+  ctx->err.clear();
+  return VRT_OK;
+}
+
+int vrt_reprojected_history_reset(vrt_ctx* ctx) {
+  if (!ctx) return VRT_ERR_INVALID;
+  ctx->rp_valid = false;
   return VRT_OK;
 }
 

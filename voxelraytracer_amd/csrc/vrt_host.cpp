@@ -233,6 +233,17 @@ int vrt_camera_make(const float pos[3], const float rot_deg[3], int32_t width, i
   return VRT_OK;
 }
 
+int vrt_camera_forward(const vrt_camera* cam, float out_pv[16]) {
+  if (!cam || !out_pv) return VRT_ERR_INVALID;
+  Mat4d a, inv;
+  for (int i = 0; i < 16; ++i) a.m[i] = double(cam->inv_pv[i]);
+  if (!invert(a, &inv)) return VRT_ERR_INVALID;
+  for (int i = 0; i < 16; ++i)
+    if (!std::isfinite(inv.m[i]) || !std::isfinite(float(inv.m[i]))) return VRT_ERR_INVALID;
+  for (int i = 0; i < 16; ++i) out_pv[i] = float(inv.m[i]);
+  return VRT_OK;
+}
+
 void vrt_sun_dir(float time_of_day, float day_time, float out[3]) {
   // Vec2f dir{1,0}; dir.Rotate(timeOfDay*pi*2/dayTime); u_SunDir = normalize(dir.y, dir.x, 0.2)
   const double a = double(time_of_day) * M_PI * 2.0 / double(day_time);

@@ -126,6 +126,25 @@ void launch_ray_trace(const KArgs& a, int32_t kind, const uint16_t* vox, const v
 // one-wave workgroup. ev_begin / ev_end: optional device timestamps, as launch_render's
 void launch_render_ids(const KArgs& a, const uint16_t* vox, vrt_pixel_id* ids, float* depth, hipStream_t s,
                        hipEvent_t ev_begin = nullptr, hipEvent_t ev_end = nullptr);
+// reproject_kernel (vrt_reproject_kernels.h): the band `a` describes (make_args with row_step 1, as
+// launch_render_ids; a.pitch pixels between band rows of raw, ids, depth, out and src), one launch, a 16x16
+// tile per workgroup of kReprojWg threads. prev / prev_ids: the whole previous frame, prev_pitch pixels
+// between rows, both null for "no history"; src may be null. ev_begin / ev_end: optional device timestamps
+struct ReprojArgs {
+  float pv[16];  // the previous frame's PV = inverse(inv_pv), column-major (vrt_camera_forward)
+  float alpha;
+  int32_t prev_pitch;
+  const uint32_t* raw;
+  const uint2* ids;
+  const float* depth;
+  const uint32_t* prev;
+  const uint2* prev_ids;
+  uint32_t* out;
+  int32_t* src;
+};
+constexpr int kReprojWg = 256;
+void launch_reproject(const KArgs& a, const ReprojArgs& r, hipStream_t s, hipEvent_t ev_begin = nullptr,
+                      hipEvent_t ev_end = nullptr);
 // fold the counter replicas into dst (accumulating) and re-zero them
 void launch_reduce_counters(unsigned long long* rep, unsigned long long* dst, hipStream_t s);
 // in-place edit of the box [lo, lo + ext) (vrt_update_volume_region), inside [0, N)^3:

@@ -3,8 +3,8 @@
 // holds the pixel epilogue, the tile order, the primary ray, the bounce-stack exact_pixel, the two
 // frame kernels and the host launch wrappers; the rest is in the headers included below, in
 // dependency order (vrt_tuning.h through vrt_internal.h), and in vrt_query_kernels.h,
-// vrt_trace_kernels.h and vrt_ids_kernels.h (the ray-query, shaded ray-query and ID-pass kernels,
-// included after the primary ray and exact_pixel they call).
+// vrt_trace_kernels.h, vrt_ids_kernels.h and vrt_reproject_kernels.h (the ray-query, shaded ray-query,
+// ID-pass and reprojected-filter kernels, included after the primary ray and exact_pixel they call).
 //
 // One work-item per pixel; a 128-thread workgroup covers a 16x8 pixel tile and each wave64 an
 // 8x8 sub-tile, so the 64 rays of a wave start coherent. Every float operation of the DDA is
@@ -703,6 +703,8 @@ __global__ void __launch_bounds__(64, WAVES) exact_pass_kernel(KArgs a, const ui
 #include "vrt_trace_kernels.h"
 // the ID and depth pass (vrt_render_ids*): after primary_ray and the ray-query kernel's ray_hit_face
 #include "vrt_ids_kernels.h"
+// the reprojected temporal filter (vrt_reproject_temporal_async): after temporal_blend and primary_ray
+#include "vrt_reproject_kernels.h"
 
 namespace vrt {
 
@@ -811,6 +813,14 @@ void launch_render_ids(const KArgs& a, const uint16_t* vox, vrt_pixel_id* ids, f
                           reinterpret_cast<uint2*>(ids), depth);
   else
     hipLaunchKernelGGL(ids_exact_kernel, grid, dim3(64), 0, s, a, vox, reinterpret_cast<uint2*>(ids), depth);
+}
+
+void launch_reproject(const KArgs& a, const ReprojArgs& r, hipStream_t s, hipEvent_t ev_begin, hipEvent_t ev_end) {
+  const dim3 grid(uint32_t(a.width + 15) / 16u, uint32_t(a.rows + 15) / 16u);
+  if (ev_begin || ev_end)
+    hipExtLaunchKernelGGL(reproject_kernel, grid, dim3(kReprojWg), 0, s, ev_begin, ev_end, 0, a, r);
+  else
+    hipLaunchKernelGGL(reproject_kernel, grid, dim3(kReprojWg), 0, s, a, r);
 }
 
 void launch_reduce_counters(unsigned long long* rep, unsigned long long* dst, hipStream_t s) {
