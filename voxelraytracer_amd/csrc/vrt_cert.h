@@ -101,6 +101,34 @@ __device__ __forceinline__ bool cert_event(uint32_t b, uint32_t medium) {
   return SHADOW ? (b & ~2u) != 0u : b != medium;
 }
 
+// What the certified pass (LEAN) hands a walk of its prologue, so that the walk does not form it again.
+// CertStartK (the primary walk): the start's sign-folded position Ps_b = s_b P_b, its floor fl_b and
+// the sign masks m_b (0 moving up, ~0 moving down), as cert_pixel's merged start predicate computed
+// them; the start cell is int(fl_b) ^ m_b. The first planes are then (fl_b + 1 - Ps_b) |1/d_b|, the
+// landing form of the loop (proved there: bit for bit (float(c_b + u_b) - P_b) rcp_b for a cell in
+// the volume), and fl_b + 1 > Ps_b for every float (fl_b = floor(Ps_b) <= Ps_b), so sig_b >= 0: the
+// loop's precondition "no plane behind the start" holds by construction.
+struct CertStartK {
+  f3 Ps, fl;
+  int mx, my, mz;
+};
+// The launch's arguments read again where the certified pass (LEAN) first needs them, after the
+// primary walk: KArgs is the kernels' first argument, at offset 0 of the kernarg segment, and the
+// pointer is kept opaque so that the scalar loads through it are not hoisted back above the walk. The
+// sun, the sky factor and the atlas constants copied into Ctx before the primary ray (init_ctx) were
+// 13 SGPRs live across the primary walk, and the frame's outputs six more across both walks: the
+// budget the certified pass's SGPR spills came from (DESIGN.md §6).
+typedef const __attribute__((address_space(4))) KArgs LateKArgs;
+__device__ __forceinline__ LateKArgs* late_kargs() {
+  LateKArgs* ka = (LateKArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(ka));
+  return ka;
+}
+// The shadow walk's functions of the sun alone are such arguments (KArgs::sun_*, formed once per launch
+// on the host, sun_consts in vrt_context.cpp: IEEE single operations in the kernel's order, no
+// contraction): a LateKArgs pointer handed to cert_shade_hit<.., KAX> and on to its cert_walk stands for
+// "read them from the launch". sun_ok is fast_path_ok(sun_n); the other fields mean something only then.
+
 // Certified walk from P along D (every |d| in the fast-path range) with rcp ~ 1/D (a few ulp
 // suffice: the walk's own rounding is inside the 4e-5 allowance of the bound), starting in cell
 // (cx, cy, cz) inside the volume. U = max_len - len0: the exact walk samples the crossing at u iff
@@ -148,7 +176,9 @@ __device__ __forceinline__ bool cert_event(uint32_t b, uint32_t medium) {
 template <bool SHADOW, bool LEAN = false, bool ED = true>
 __device__ __forceinline__ CertResult cert_walk(const Ctx& c, const f3 P, const f3 D, const f3 rcp, const float U,
                                 int cx, int cy, int cz, const float e0, const f3 ed,
-                                const float len0b, const uint32_t medium, const uint32_t tex0 = ~0u) {
+                                const float len0b, const uint32_t medium, const uint32_t tex0 = ~0u,
+                                const CertStartK* __restrict__ st0 = nullptr,
+                                LateKArgs* sk = nullptr) {
   CertResult r;
   r.res = CERT_UNSURE;
   r.byte = 0u;
@@ -157,11 +187,16 @@ __device__ __forceinline__ CertResult cert_walk(const Ctx& c, const f3 P, const 
   r.u = 0.0f;
   r.eu = 0.0f;
   r.us = 0.0f;
-  const int sx = D.x > 0.0f ? 1 : -1, sy = D.y > 0.0f ? 1 : -1, sz = D.z > 0.0f ? 1 : -1;
-  const int ux = D.x > 0.0f ? 1 : 0, uy = D.y > 0.0f ? 1 : 0, uz = D.z > 0.0f ? 1 : 0;
+  // (sk: the shadow walk's direction is the sun: its signs, octant and |S|_1 are launch constants)
+  const bool ksun = LEAN && sk != nullptr;
+  const int sx = ksun ? sk->sun_step[0] : (D.x > 0.0f ? 1 : -1), sy = ksun ? sk->sun_step[1] : (D.y > 0.0f ? 1 : -1),
+            sz = ksun ? sk->sun_step[2] : (D.z > 0.0f ? 1 : -1);
+  const int ux = ksun ? (sk->sun_step[0] > 0 ? 1 : 0) : (D.x > 0.0f ? 1 : 0), uy = ksun ? (sk->sun_step[1] > 0 ? 1 : 0) : (D.y > 0.0f ? 1 : 0),
+            uz = ksun ? (sk->sun_step[2] > 0 ? 1 : 0) : (D.z > 0.0f ? 1 : 0);
   const f3 ar = mk(__builtin_fabsf(rcp.x), __builtin_fabsf(rcp.y), __builtin_fabsf(rcp.z));
-  const float l1 = __builtin_fabsf(D.x) + __builtin_fabsf(D.y) + __builtin_fabsf(D.z);
-  const uint32_t obase = ((D.x < 0.0f ? 1u : 0u) | (D.y < 0.0f ? 2u : 0u) | (D.z < 0.0f ? 4u : 0u)) * c.ostride;
+  const float l1 = ksun ? sk->sun_l1 : __builtin_fabsf(D.x) + __builtin_fabsf(D.y) + __builtin_fabsf(D.z);
+  const uint32_t obase =
+      ksun ? sk->sun_obase : ((D.x < 0.0f ? 1u : 0u) | (D.y < 0.0f ? 2u : 0u) | (D.z < 0.0f ? 4u : 0u)) * c.ostride;
   // Rounding bounds as polynomials in the crossing parameter u (2x safety factor on 2^-24):
   //   K(u) = u |d|_1 + 3 non-zero exact steps, sum_k len_k <= (K + 3)^2 / (2 |d|_1) + K (len0 + 1),
   //   gam_b(u) = 2^-24 (sum len + 2 (u + len0) + (K + 3N + 8) |1/d_b|) + 4e-5 + e0 + ed_b,
@@ -169,20 +204,27 @@ __device__ __forceinline__ CertResult cert_walk(const Ctx& c, const f3 P, const 
   // Factored by what depends on the axis: gam_b(u) = A(u) + |1/d_b| B(u) + ed_b,
   //   A(u) = (q2 u + a1) u + c0, B(u) = b1 u + b0: five scalars per walk, three fma per iteration
   constexpr float k24 = 2.0f * 0x1p-24f;
-  const float q2 = 0.5f * k24 * l1;
+  const float q2 = ksun ? sk->sun_q2 : 0.5f * k24 * l1;
   // 18 / |d|_1 only bounds a sum: the hardware reciprocal (<= 1 ulp) scaled up by 2^-19 stays above it
   const float lin = 6.0f + l1 * (len0b + 1.0f),
               con = (18.0f * 1.0000020f) * __builtin_amdgcn_rcpf(l1) + 3.0f * (len0b + 1.0f);
-  const float a1 = k24 * (lin + 2.0f), b1 = k24 * l1, b0 = k24 * (3.0f * c.fn + 11.0f);
+  const float a1 = k24 * (lin + 2.0f), b1 = ksun ? sk->sun_b1 : k24 * l1, b0 = k24 * (3.0f * c.fn + 11.0f);
   const float c0 = k24 * (con + 2.0f * len0b) + 4e-5f + e0;
-  const float g2 = 2.0f * q2, g1 = 2.0f * k24 * lin, g0 = 2.0f * k24 * con + 1e-4f + e0;
+  const float g2 = ksun ? sk->sun_g2 : 2.0f * q2, g1 = 2.0f * k24 * lin, g0 = 2.0f * k24 * con + 1e-4f + e0;
   // sign-folded start and direction: Ps_b + u |d_b| = s_b (P_b + u d_b) exactly (negation is exact),
   // so a landing cell is floor(s x) ^ m, m = 0 or ~0 (ceil(x) - 1 = ~floor(-x)), without branches
-  const f3 Ps = mk(ux ? P.x : -P.x, uy ? P.y : -P.y, uz ? P.z : -P.z);
+  // (st0: the caller's start formed them; sk: the negation as the launch's sign bit, one xor)
+  const bool kst = LEAN && st0 != nullptr;
+  const f3 Ps = kst    ? st0->Ps
+                : ksun ? mk(__uint_as_float(__float_as_uint(P.x) ^ sk->sun_neg[0]), __uint_as_float(__float_as_uint(P.y) ^ sk->sun_neg[1]),
+                            __uint_as_float(__float_as_uint(P.z) ^ sk->sun_neg[2]))
+                       : mk(ux ? P.x : -P.x, uy ? P.y : -P.y, uz ? P.z : -P.z);
   const f3 Da = mk(__builtin_fabsf(D.x), __builtin_fabsf(D.y), __builtin_fabsf(D.z));
-  const int mx = ux - 1, my = uy - 1, mz = uz - 1;
-  f3 sig = mk((float(cx + ux) - P.x) * rcp.x, (float(cy + uy) - P.y) * rcp.y,
-              (float(cz + uz) - P.z) * rcp.z);
+  const int mx = kst ? st0->mx : ux - 1, my = kst ? st0->my : uy - 1, mz = kst ? st0->mz : uz - 1;
+  // (st0: the first planes from the start's floored floats, the landing form below: CertStartK)
+  f3 sig = kst ? mk(((st0->fl.x + 1.0f) - Ps.x) * ar.x, ((st0->fl.y + 1.0f) - Ps.y) * ar.y,
+                    ((st0->fl.z + 1.0f) - Ps.z) * ar.z)
+               : mk((float(cx + ux) - P.x) * rcp.x, (float(cy + uy) - P.y) * rcp.y, (float(cz + uz) - P.z) * rcp.z);
   // start: the unguarded box from the diagonal neighbour (G(v + s) + 1 in the guarded formula)
   // (tex0: that texel, loaded by the caller beside an earlier load; ~0u: load it here)
   uint32_t tex = (tex0 != ~0u ? tex0
@@ -493,23 +535,60 @@ __device__ __forceinline__ Hit cert_hit_record(const Ray& ray, const CertResult&
 // TraceWithShadow's colour update (voxel.glsl:395-418) for a certified hit of `ray`: the shadow
 // bit by a certified shadow walk from the hit, unless it cannot change the brightness (lit ==
 // ambient). false: unsure (colour untouched).
-template <bool TEX = false, bool LEAN = false>
+template <bool TEX = false, bool LEAN = false, bool KAX = false>
 __device__ __forceinline__ bool cert_shade_hit(const Ctx& c, const Ray& ray, const CertResult& h,
-                                               const Hit& hh, f3& color, float4 col = float4()) {
-  const float lit = lit_brightness<TEX>(hh, c.sun_n, ray.dir);
+                                               const Hit& hh, f3& color, float4 col = float4(),
+                                               LateKArgs* sk = nullptr) {
+  const f3 S = c.sun_n;
+  // KAX (the certified pass's primary hits; LEAN): sk holds the sun's launch constants. With sk->sun_ok (wave-uniform:
+  // every |S_b| in fast_path_ok's range, so no component of S is zero) the lit term takes the face's
+  // axis normal n = -sign(D_a) e_a as what it is (ray.dir is in the fast-path range too: D_a != 0):
+  //  - dot(n, S) = (n_x S_x + n_y S_y) + n_z S_z has two terms +-0 and the term n_a S_a = -+S_a != 0,
+  //    and x + +-0 = x for x != 0: the sum is n_a S_a, the select below, bit for bit;
+  //  - reflect(S, n) = S - (2 dot(n, S)) n: component a is S_a - 2 S_a = -S_a exactly, component b is
+  //    S_b - (+-0) = S_b (S_b != 0), so dot(reflect(S, n), D) = (p_x + p_y) + p_z with p_b = S_b D_b and
+  //    p_a = (-S_a) D_a = -(S_a D_a) (negation commutes with rounding): the same products, the same order.
+  // With a zero in S the zeros' signs can differ (-0 - -0 = +0: tests/test_cert_start_lit_forms.py finds
+  // such suns), so the generic form stays behind the wave-uniform branch; it defers every lit hit there.
+  float lit, ns = 0.0f;
+  if constexpr (KAX) {
+    if (sk->sun_ok != 0u) {
+      const int a = h.axis;
+      // (the direction as opaque values: in the tree instances, where the ray lives in memory, the
+      // select of its fields became a load at a selected address and kept the ray in scratch, 48 B)
+      f3 D = ray.dir;
+      asm volatile("" : "+v"(D.x), "+v"(D.y), "+v"(D.z));
+      const float sa = a == 0 ? S.x : (a == 1 ? S.y : S.z), da = a == 0 ? D.x : (a == 1 ? D.y : D.z);
+      ns = da > 0.0f ? -sa : sa;
+      const float px = S.x * D.x, py = S.y * D.y, pz = S.z * D.z;
+      const float rd = ((a == 0 ? -px : px) + (a == 1 ? -py : py)) + (a == 2 ? -pz : pz);
+      const uint32_t m = mat_id(h.byte);
+      const float diffuse = mat_kd(m) * gmax(ns, 0.0f);
+      const float specular = mat_ks(m, TEX) * gpow(gmax(rd, 0.0f), mat_exp(m, TEX));
+      lit = kAmbient + diffuse + specular;
+    } else {
+      lit = lit_brightness<TEX>(hh, S, ray.dir);
+    }
+  } else {
+    lit = lit_brightness<TEX>(hh, S, ray.dir);
+  }
   float brightness = kAmbient;
   if (lit != kAmbient && !shadow_free_hit(h.byte, TEX)) {  // otherwise the brightness is the ambient term (or irrelevant)
-    const f3 S = c.sun_n;
-    if (!(dot3(hh.normal, S) > 0.0f) || !fast_path_ok(S)) { CERT_DIAG(5); return false; }  // back face
+    if constexpr (KAX) {  // back face, or a sun outside the fast-path range (sk->sun_ok is fast_path_ok(S))
+      if (sk->sun_ok == 0u || !(ns > 0.0f)) { CERT_DIAG(5); return false; }
+    } else {
+      if (!(dot3(hh.normal, S) > 0.0f) || !fast_path_ok(S)) { CERT_DIAG(5); return false; }  // back face
+    }
     // shadow origin: the exact hit point; start cell: the air cell in front of the hit face
     int ax, ay, az;
     cell_before(h, ray.dir, ax, ay, az);
     // the shadow walk's start texel (the diagonal neighbour in the sun's octant volume) is loaded
     // first, so its latency overlaps the start checks and the air-cell load (same octant volume:
     // every octant volume holds the same voxel bytes)
-    const uint32_t sob = ((S.x < 0.0f ? 1u : 0u) | (S.y < 0.0f ? 2u : 0u) | (S.z < 0.0f ? 4u : 0u)) * c.ostride;
-    const uint32_t t0 = path_texel(c, ax + (S.x > 0.0f ? 1 : -1), ay + (S.y > 0.0f ? 1 : -1),
-                                   az + (S.z > 0.0f ? 1 : -1), sob);
+    const uint32_t sob =
+        KAX ? sk->sun_obase : ((S.x < 0.0f ? 1u : 0u) | (S.y < 0.0f ? 2u : 0u) | (S.z < 0.0f ? 4u : 0u)) * c.ostride;
+    const uint32_t t0 = path_texel(c, ax + (KAX ? sk->sun_step[0] : (S.x > 0.0f ? 1 : -1)), ay + (KAX ? sk->sun_step[1] : (S.y > 0.0f ? 1 : -1)),
+                                   az + (KAX ? sk->sun_step[2] : (S.z > 0.0f ? 1 : -1)), sob);
     f3 ed;
     if (!cert_start(hh.point, ray.dir, S, c.sun_rcp, h.axis, h.eu, ax, ay, az, ed)) {
       CERT_DIAG(6);
@@ -519,7 +598,7 @@ __device__ __forceinline__ bool cert_shade_hit(const Ctx& c, const Ray& ray, con
     if (uint32_t(ax) >= n || uint32_t(ay) >= n || uint32_t(az) >= n) { CERT_DIAG(7); return false; }
     if (cert_event<true>(cell_texel(c, ax, ay, az, sob) & kVoxMask, 0u)) { CERT_DIAG(7); return false; }
     const CertResult s = cert_walk<true, LEAN>(c, hh.point, S, c.sun_rcp, c.max_len - hh.len, ax, ay, az,
-                                         h.eu, ed, hh.len, 0u, t0);
+                                         h.eu, ed, hh.len, 0u, t0, nullptr, KAX ? sk : nullptr);
     if (LEAN && (PHASE_STOP(4) || PHASE_STOP(5))) {  // phase budget: the shadow walk's result as the colour
       color = mk(s.u + float(s.res), lit + float(s.cx), 0.0f);
       return true;
@@ -954,6 +1033,14 @@ __device__ __forceinline__ bool cert_continuation(const Ctx& c, const Ray& ray, 
     if ((fa != 0 && wpx != float(cx + (sx > 0))) || (fa != 1 && wpy != float(cy + (sy > 0))) ||
         (fa != 2 && wpz != float(cz + (sz > 0))))
       return false;
+    // Another axis b on a plane and moving down (P_b an integer, D_b < 0) puts the cell above at
+    // P_b - 1, but the exact walk samples the layer beyond the plane until cur_b rounds off it, as at
+    // a fresh start (start_layers_clear). That layer is not checked here: unsure. (A camera straight
+    // above glass clutter, z = 16.0 and D_z = -6e-17 after each refraction: the continuations walked
+    // layer 15 while the exact walk stayed in layer 16 to the end; one pixel of the frame differed.)
+    if ((fa != 0 && D.x < 0.0f && P.x == __builtin_floorf(P.x)) || (fa != 1 && D.y < 0.0f && P.y == __builtin_floorf(P.y)) ||
+        (fa != 2 && D.z < 0.0f && P.z == __builtin_floorf(P.z)))
+      return false;
     const int ka = int(k) - (da > 0.0f ? 0 : 1);
     if (fa == 0) cx = ka;
     else if (fa == 1) cy = ka;
@@ -1103,18 +1190,6 @@ __device__ __forceinline__ bool cert_texel(const Ctx& c, const Ray& ray, const C
   return true;
 }
 
-// The launch's arguments read again where the certified pass (LEAN) first needs them, after the
-// primary walk: KArgs is the kernels' first argument, at offset 0 of the kernarg segment, and the
-// pointer is kept opaque so that the scalar loads through it are not hoisted back above the walk. The
-// sun, the sky factor and the atlas constants copied into Ctx before the primary ray (init_ctx) were
-// 13 SGPRs live across the primary walk, and the frame's outputs six more across both walks: the
-// budget the certified pass's SGPR spills came from (DESIGN.md §6).
-typedef const __attribute__((address_space(4))) KArgs LateKArgs;
-__device__ __forceinline__ LateKArgs* late_kargs() {
-  LateKArgs* ka = (LateKArgs*)__builtin_amdgcn_kernarg_segment_ptr();
-  asm volatile("" : "+s"(ka));
-  return ka;
-}
 // the Ctx fields init_ctx<true> leaves out: the same values from the same words
 __device__ __forceinline__ void late_ctx(Ctx& c) {
   LateKArgs* ka = late_kargs();
@@ -1126,7 +1201,6 @@ __device__ __forceinline__ void late_ctx(Ctx& c) {
   c.atlas_fs = float(ka->atlas_size);
   c.atlas_fts = float(ka->atlas_tex_size);
 }
-
 // TREE (colour-only): a glass primary hit's bounce tree by certified walks too (cert_tree; ltb and c.ax its
 // LDS slot), instead of leaving the whole pixel to the exact path.
 // us_out: the primary walk's certified prefix (CertResult::us) for the exact path, -1 if none.
@@ -1135,16 +1209,47 @@ __device__ __forceinline__ bool cert_pixel(const Ctx& c0, const Ray& ray0, f3& c
                                            int max_transp = 0, float* __restrict__ ltb = nullptr,
                                            float* us_out = nullptr) {
   const f3 P = ray0.pos, D = ray0.dir;
-  if (!fast_path_ok(D)) { CERT_DIAG(0); return false; }
   int cx, cy, cz;
-  if (!exact_start_cell(c0, P, D, cx, cy, cz) || !start_layers_clear<false>(c0, P, D, cx, cy, cz, 0u)) {
-    CERT_DIAG(0);
-    return false;
+  CertStartK st;
+  if constexpr (LEAN) {
+    // The start as one predicate, sign-folded as the walk is: q_b = s_b P_b, fl_b = floor(q_b), the cell
+    // int(fl_b) ^ m_b. Negation commutes with rounding, so moving down floor(-P) = -ceil(P): the cell
+    // ~floor(-P) is ceil(P) - 1 and the plane test floor(-P + 1) == floor(-P) + 1 is ceil(P - 1) ==
+    // float(ceil(P) - 1) negated on both sides. Moving up it is exact_start_cell's own test: for a cell
+    // in the volume float(c + 1) = fl + 1 exactly, and for any other cell the bounds fail in both forms.
+    // fast_path_ok(D), the bounds and the planes are ANDed without a branch; the cells mean something
+    // only when the predicate holds. The on-plane trigger, start_layers_clear's per-axis entry test
+    // (D_b < 0 and P_b an integer: fast_path_ok excludes D_b = 0, where D_b < 0 and !(D_b > 0) differ),
+    // puts that function, unchanged, behind one region.
+    // (tests/test_cert_start_lit_forms.py: both forms over the sign octants and the edge positions)
+    const bool ux = D.x > 0.0f, uy = D.y > 0.0f, uz = D.z > 0.0f;
+    st.Ps = mk(ux ? P.x : -P.x, uy ? P.y : -P.y, uz ? P.z : -P.z);
+    st.fl = mk(__builtin_floorf(st.Ps.x), __builtin_floorf(st.Ps.y), __builtin_floorf(st.Ps.z));
+    st.mx = ux ? 0 : -1;
+    st.my = uy ? 0 : -1;
+    st.mz = uz ? 0 : -1;
+    cx = int(st.fl.x) ^ st.mx;
+    cy = int(st.fl.y) ^ st.my;
+    cz = int(st.fl.z) ^ st.mz;
+    bool ok = int(fast_path_ok(D)) & int(max(max(uint32_t(cx), uint32_t(cy)), uint32_t(cz)) < uint32_t(c0.n)) &
+              int(__builtin_floorf(st.Ps.x + 1.0f) == st.fl.x + 1.0f) &
+              int(__builtin_floorf(st.Ps.y + 1.0f) == st.fl.y + 1.0f) &
+              int(__builtin_floorf(st.Ps.z + 1.0f) == st.fl.z + 1.0f);
+    const bool on_plane = (int(!ux) & int(st.fl.x == st.Ps.x)) | (int(!uy) & int(st.fl.y == st.Ps.y)) |
+                          (int(!uz) & int(st.fl.z == st.Ps.z));
+    if (ok & on_plane) ok = start_layers_clear<false>(c0, P, D, cx, cy, cz, 0u);
+    if (!ok) { CERT_DIAG(0); return false; }
+  } else {
+    if (!fast_path_ok(D)) { CERT_DIAG(0); return false; }
+    if (!exact_start_cell(c0, P, D, cx, cy, cz) || !start_layers_clear<false>(c0, P, D, cx, cy, cz, 0u)) {
+      CERT_DIAG(0);
+      return false;
+    }
   }
   // hardware reciprocals (<= 1 ulp): the certified walk only needs its own error bounded
   const f3 rcp = mk(__builtin_amdgcn_rcpf(D.x), __builtin_amdgcn_rcpf(D.y), __builtin_amdgcn_rcpf(D.z));
   CertResult h = cert_walk<false, LEAN, false>(c0, P, D, rcp, c0.max_len - ray0.len, cx, cy, cz, 0.0f,
-                                               mk(0.0f, 0.0f, 0.0f), 0.0f, 0u);
+                                               mk(0.0f, 0.0f, 0.0f), 0.0f, 0u, ~0u, LEAN ? &st : nullptr);
   if (us_out) *us_out = h.us;
   CERT_DIAG_ONLY(cert_diag_iters(10, h.iters);)
   if (LEAN && (PHASE_STOP(2) || PHASE_STOP(3))) {  // phase budget: the primary walk's result as the colour
@@ -1169,7 +1274,11 @@ __device__ __forceinline__ bool cert_pixel(const Ctx& c0, const Ray& ray0, f3& c
   const Hit hh = cert_hit_record(ray0, h);
   float4 col = float4();
   if (TEX && !cert_texel(c, ray0, h, hh, col)) return false;
-  if (!cert_shade_hit<TEX, LEAN>(c, ray0, h, hh, color, col)) return false;
+  if constexpr (LEAN) {  // the sun's constants from the launch's arguments, read here, after the primary walk
+    if (!cert_shade_hit<TEX, true, true>(c, ray0, h, hh, color, col, late_kargs())) return false;
+  } else {
+    if (!cert_shade_hit<TEX, false>(c, ray0, h, hh, color, col)) return false;
+  }
   color_out = color;
   return true;
 }

@@ -131,6 +131,29 @@ struct Shard {
 
 }  // namespace
 
+// The shadow walk's functions of the sun alone (KArgs::sun_*), once per launch instead of once per wave:
+// the kernel's expressions (fast_path_ok, cert_walk's prologue, cert_shade_hit's octant) on the same
+// floats in the same order. Only IEEE single additions, multiplications and compares: this file is built
+// without contraction, so each value is the kernel's bit for bit (the reciprocal of l1 stays there).
+void vrt::sun_consts(KArgs& a) {
+  const float* s = a.sun_n;
+  const float lo = 0x1p-64f, hi = 1.0e4f;
+  bool ok = true;
+  for (int b = 0; b < 3; ++b) ok = ok && std::fabs(s[b]) >= lo && std::fabs(s[b]) <= hi;
+  a.sun_ok = ok ? 1u : 0u;
+  for (int b = 0; b < 3; ++b) {
+    a.sun_neg[b] = s[b] > 0.0f ? 0u : 0x80000000u;
+    a.sun_step[b] = s[b] > 0.0f ? 1 : -1;
+  }
+  a.sun_obase = ((s[0] < 0.0f ? 1u : 0u) | (s[1] < 0.0f ? 2u : 0u) | (s[2] < 0.0f ? 4u : 0u)) * a.ostride;
+  constexpr float k24 = 2.0f * 0x1p-24f;
+  const float l1 = std::fabs(s[0]) + std::fabs(s[1]) + std::fabs(s[2]);
+  a.sun_l1 = l1;
+  a.sun_q2 = 0.5f * k24 * l1;
+  a.sun_b1 = k24 * l1;
+  a.sun_g2 = 2.0f * a.sun_q2;
+}
+
 struct vrt_ctx {
   std::vector<Shard> sh;
   bool distinct = true;                 // devices pairwise distinct: RCCL communicators exist
@@ -425,19 +448,23 @@ uint32_t octant_stride(const Shard& s) {
   return s.octants == 8 ? uint32_t(uint64_t(s.n + 1) * (s.n + 1) * (s.n + 1) * sizeof(uint16_t)) : 0u;
 }
 
+// normalize(u_SunDir) exactly as the kernel's normalize3 (IEEE single ops, no contraction), and its reciprocals
+void fill_sun(vrt::KArgs& a, const float* sun_dir) {
+  const float sx = sun_dir[0], sy = sun_dir[1], sz = sun_dir[2];
+  const float inv = 1.0f / std::sqrt(sx * sx + sy * sy + sz * sz);
+  a.sun_n[0] = sx * inv;
+  a.sun_n[1] = sy * inv;
+  a.sun_n[2] = sz * inv;
+  for (int i = 0; i < 3; ++i) a.sun_rcp[i] = 1.0f / a.sun_n[i];
+}
+
 vrt::KArgs make_args(const vrt_ctx* ctx, const Shard& s, const vrt_camera* cam, const vrt_params* p,
                      int32_t row0, int32_t rows, int32_t row_step) {
   vrt::KArgs a;
   std::memcpy(a.inv_pv, cam->inv_pv, sizeof(a.inv_pv));
   std::memcpy(a.sun, p->sun_dir, sizeof(a.sun));
   a.sky_sy = std::fmax(p->sun_dir[1], 0.0f);  // GLSL max(x, 0) with fmaxf's NaN rule, as gmax
-  // normalize(u_SunDir) exactly as the kernel's normalize3 (IEEE single ops, no contraction)
-  const float sx = p->sun_dir[0], sy = p->sun_dir[1], sz = p->sun_dir[2];
-  const float inv = 1.0f / std::sqrt(sx * sx + sy * sy + sz * sz);
-  a.sun_n[0] = sx * inv;
-  a.sun_n[1] = sy * inv;
-  a.sun_n[2] = sz * inv;
-  for (int i = 0; i < 3; ++i) a.sun_rcp[i] = 1.0f / a.sun_n[i];
+  fill_sun(a, p->sun_dir);
   a.time = p->time;
   a.ray_noise = p->ray_noise;
   a.refl_noise = p->reflection_noise;
@@ -455,6 +482,7 @@ vrt::KArgs make_args(const vrt_ctx* ctx, const Shard& s, const vrt_camera* cam, 
   a.row_blk_sh = 0;
   a.pitch = cam->width;
   a.ostride = octant_stride(s);
+  vrt::sun_consts(a);  // (after sun_n and ostride)
   a.max_refl = p->max_reflections;
   a.max_transp = p->max_transparencies;
   a.textured = p->color_only ? 0 : 1;
@@ -1212,6 +1240,18 @@ int create(const std::vector<int>& devs, vrt_ctx** out) {
 }  // namespace
 
 extern "C" {
+
+// Test hook, not part of vrt.h (tests/test_cert_start_lit_forms.py): the twelve KArgs::sun_* words, in
+// the struct's order, for normalize(sun_dir) as make_args forms it. Host arithmetic only, no device.
+int vrt_debug_sun_consts(const float* sun_dir, uint32_t ostride, uint32_t* out) {
+  if (!sun_dir || !out) return VRT_ERR_INVALID;
+  vrt::KArgs a{};
+  fill_sun(a, sun_dir);
+  a.ostride = ostride;
+  vrt::sun_consts(a);
+  std::memcpy(out, &a.sun_ok, 12 * sizeof(uint32_t));
+  return VRT_OK;
+}
 
 int vrt_create(uint32_t device_mask, vrt_ctx** out) {
   std::vector<int> devs;

@@ -80,7 +80,20 @@ struct KArgs {
     uint32_t* cur;
     uint32_t* raw;
   } fb[7];
+  // The shadow walk's functions of the sun alone (sun_consts, filled where sun_n and sun_rcp are): the
+  // certified pass reads them late, after its primary walk (late_sun, vrt_cert.h); no other kernel does.
+  // sun_ok: fast_path_ok(sun_n); sun_neg[b]: 0 where sun_n[b] > 0, else the sign bit (x ^ sun_neg is
+  // the walk's sign-folded x); sun_step[b]: sun_n[b] > 0 ? 1 : -1; sun_obase: the sun's octant volume,
+  // ((x < 0) | (y < 0) << 1 | (z < 0) << 2) * ostride; sun_l1 = (|x| + |y|) + |z| and its products with
+  // k24 = 2^-23 as cert_walk forms them: q2 = 0.5 k24 l1, b1 = k24 l1, g2 = 2 q2 (IEEE single, in that order)
+  uint32_t sun_ok;
+  uint32_t sun_neg[3];
+  int32_t sun_step[3];
+  uint32_t sun_obase;
+  float sun_l1, sun_q2, sun_b1, sun_g2;
 };
+// fills the sun_* constants above from a.sun_n and a.ostride (host, vrt_context.cpp)
+void sun_consts(KArgs& a);
 constexpr int kMaxBatch = 8;  // frames per launch (1 + the fb entries)
 constexpr int kWgThreads = 64 * kWgWaves;  // kWgWaves: vrt_tuning.h
 constexpr int kTileW = kWgWaves >= 2 ? 16 : 8;  // a workgroup's pixel tile: 16x16, 16x8 or 8x8

@@ -490,7 +490,12 @@ __global__ void __launch_bounds__(kWgThreads, TREE ? kTreeWaves : (DEFER ? kDefe
     // WRITE_SIZE 41 -> 17 MB per frame at equal speed (profiles/r02_s03). Parking the certified
     // colour in LDS, or storing certified pixels before the exact path and re-deriving the
     // primary ray there, was 4-6 % slower.
-    f3 color = mk(0.0f, 0.0f, 0.0f);
+    // DEFER: the colour has no value until cert_pixel certifies the pixel and writes it; a deferred
+    // pixel's colour is never stored here, and a zero was materialised before each of cert_pixel's
+    // nested early exits (11 times three moves on the every-pixel path). The in-lane instances keep
+    // their zero: exact_pixel starts from it.
+    f3 color;
+    if constexpr (!DEFER) color = mk(0.0f, 0.0f, 0.0f);
     float* tstk = nullptr;
     if constexpr (TREE) {
       static_assert(CERT == 2 && !TEX && !STATS, "certified trees: stats-free colour-only certified instances");
@@ -499,7 +504,8 @@ __global__ void __launch_bounds__(kWgThreads, TREE ? kTreeWaves : (DEFER ? kDefe
     float us = -1.0f;  // the primary walk's certified prefix, for the exact path
     bool need_exact;
     if (DEFER && (PHASE_STOP(0) || PHASE_STOP(1))) {  // phase budget: nothing, or the ray alone, as the colour
-      if (PHASE_STOP(1)) color = mk(ray.pos.x + ray.dir.x, ray.pos.y + ray.dir.y, ray.pos.z + ray.dir.z);
+      color = PHASE_STOP(1) ? mk(ray.pos.x + ray.dir.x, ray.pos.y + ray.dir.y, ray.pos.z + ray.dir.z)
+                            : mk(0.0f, 0.0f, 0.0f);
       need_exact = false;
     } else {
       need_exact = CERT < 2 || !cert_pixel<TEX, TREE, kWgThreads, DEFER>(c, ray, color, a.max_refl, a.max_transp, tstk, &us);
