@@ -102,15 +102,19 @@ __device__ __forceinline__ bool cert_event(uint32_t b, uint32_t medium) {
 }
 
 // What the certified pass (LEAN) hands a walk of its prologue, so that the walk does not form it again.
-// CertStartK (the primary walk): the start's sign-folded position Ps_b = s_b P_b, its floor fl_b and
-// the sign masks m_b (0 moving up, ~0 moving down), as cert_pixel's merged start predicate computed
-// them; the start cell is int(fl_b) ^ m_b. The first planes are then (fl_b + 1 - Ps_b) |1/d_b|, the
-// landing form of the loop (proved there: bit for bit (float(c_b + u_b) - P_b) rcp_b for a cell in
-// the volume), and fl_b + 1 > Ps_b for every float (fl_b = floor(Ps_b) <= Ps_b), so sig_b >= 0: the
-// loop's precondition "no plane behind the start" holds by construction.
+// CertStartK (the primary walk): the start's sign-folded position Ps_b = s_b P_b, its floor plus one
+// fl1_b = fl_b + 1 (exact: an integer far below 2^24) and the sign masks m_b (0 moving up, ~0 moving down),
+// as cert_pixel's merged start predicate computed them; the start cell is int(fl_b) ^ m_b. The first planes
+// are then (fl_b + 1 - Ps_b) |1/d_b|, the landing form of the loop (proved there: bit for bit (float(c_b +
+// u_b) - P_b) rcp_b for a cell in the volume), and fl_b + 1 > Ps_b for every float (fl_b = floor(Ps_b) <=
+// Ps_b), so sig_b >= 0: the loop's precondition "no plane behind the start" holds by construction. (With the
+// launch's start cell proved on the host, KArgs::setup & kSetupCell, fl1_b is a select of two launch
+// constants; fl_b < Ps_b < fl_b + 1 is then part of the proof.)
+// b0, U2: the launch's k24 (3 fn + 11) and max_len + 2 (KArgs::walk_b0, max_len2), which the walk would form.
 struct CertStartK {
-  f3 Ps, fl;
+  f3 Ps, fl1;
   int mx, my, mz;
+  float b0, U2;
 };
 // The launch's arguments read again where the certified pass (LEAN) first needs them, after the
 // primary walk: KArgs is the kernels' first argument, at offset 0 of the kernarg segment, and the
@@ -189,6 +193,7 @@ __device__ __forceinline__ CertResult cert_walk(const Ctx& c, const f3 P, const 
   r.us = 0.0f;
   // (sk: the shadow walk's direction is the sun: its signs, octant and |S|_1 are launch constants)
   const bool ksun = LEAN && sk != nullptr;
+  const bool kst = LEAN && st0 != nullptr;  // (st0: the primary walk's start and launch constants, CertStartK)
   const int sx = ksun ? sk->sun_step[0] : (D.x > 0.0f ? 1 : -1), sy = ksun ? sk->sun_step[1] : (D.y > 0.0f ? 1 : -1),
             sz = ksun ? sk->sun_step[2] : (D.z > 0.0f ? 1 : -1);
   const int ux = ksun ? (sk->sun_step[0] > 0 ? 1 : 0) : (D.x > 0.0f ? 1 : 0), uy = ksun ? (sk->sun_step[1] > 0 ? 1 : 0) : (D.y > 0.0f ? 1 : 0),
@@ -208,13 +213,13 @@ __device__ __forceinline__ CertResult cert_walk(const Ctx& c, const f3 P, const 
   // 18 / |d|_1 only bounds a sum: the hardware reciprocal (<= 1 ulp) scaled up by 2^-19 stays above it
   const float lin = 6.0f + l1 * (len0b + 1.0f),
               con = (18.0f * 1.0000020f) * __builtin_amdgcn_rcpf(l1) + 3.0f * (len0b + 1.0f);
-  const float a1 = k24 * (lin + 2.0f), b1 = ksun ? sk->sun_b1 : k24 * l1, b0 = k24 * (3.0f * c.fn + 11.0f);
+  const float a1 = k24 * (lin + 2.0f), b1 = ksun ? sk->sun_b1 : k24 * l1,
+              b0 = kst ? st0->b0 : (ksun ? sk->walk_b0 : k24 * (3.0f * c.fn + 11.0f));
   const float c0 = k24 * (con + 2.0f * len0b) + 4e-5f + e0;
   const float g2 = ksun ? sk->sun_g2 : 2.0f * q2, g1 = 2.0f * k24 * lin, g0 = 2.0f * k24 * con + 1e-4f + e0;
   // sign-folded start and direction: Ps_b + u |d_b| = s_b (P_b + u d_b) exactly (negation is exact),
   // so a landing cell is floor(s x) ^ m, m = 0 or ~0 (ceil(x) - 1 = ~floor(-x)), without branches
   // (st0: the caller's start formed them; sk: the negation as the launch's sign bit, one xor)
-  const bool kst = LEAN && st0 != nullptr;
   const f3 Ps = kst    ? st0->Ps
                 : ksun ? mk(__uint_as_float(__float_as_uint(P.x) ^ sk->sun_neg[0]), __uint_as_float(__float_as_uint(P.y) ^ sk->sun_neg[1]),
                             __uint_as_float(__float_as_uint(P.z) ^ sk->sun_neg[2]))
@@ -222,8 +227,7 @@ __device__ __forceinline__ CertResult cert_walk(const Ctx& c, const f3 P, const 
   const f3 Da = mk(__builtin_fabsf(D.x), __builtin_fabsf(D.y), __builtin_fabsf(D.z));
   const int mx = kst ? st0->mx : ux - 1, my = kst ? st0->my : uy - 1, mz = kst ? st0->mz : uz - 1;
   // (st0: the first planes from the start's floored floats, the landing form below: CertStartK)
-  f3 sig = kst ? mk(((st0->fl.x + 1.0f) - Ps.x) * ar.x, ((st0->fl.y + 1.0f) - Ps.y) * ar.y,
-                    ((st0->fl.z + 1.0f) - Ps.z) * ar.z)
+  f3 sig = kst ? mk((st0->fl1.x - Ps.x) * ar.x, (st0->fl1.y - Ps.y) * ar.y, (st0->fl1.z - Ps.z) * ar.z)
                : mk((float(cx + ux) - P.x) * rcp.x, (float(cy + uy) - P.y) * rcp.y, (float(cz + uz) - P.z) * rcp.z);
   // start: the unguarded box from the diagonal neighbour (G(v + s) + 1 in the guarded formula)
   // (tex0: that texel, loaded by the caller beside an earlier load; ~0u: load it here)
@@ -272,7 +276,7 @@ __device__ __forceinline__ CertResult cert_walk(const Ctx& c, const f3 P, const 
                   jz = __builtin_fmaf(fb, ar.z, sig.z);
       const float jm = ED ? __builtin_fminf(jx - ed.x, __builtin_fminf(jy - ed.y, jz - ed.z))
                           : __builtin_fminf(jx, __builtin_fminf(jy, jz));
-      const float uj = __builtin_fminf(jm - A, U + 2.0f);
+      const float uj = __builtin_fminf(jm - A, kst ? st0->U2 : U + 2.0f);
       CTRACE(c, 102, G, s1, uj, gam_of(ar.x, ed.x), gam_of(ar.y, ed.y), gam_of(ar.z, ed.z), 0);
       if (uj > s1) {
         // the cell the exact walk is in there: floor(x) moving up, ceil(x) - 1 moving down
@@ -1204,10 +1208,11 @@ __device__ __forceinline__ void late_ctx(Ctx& c) {
 // TREE (colour-only): a glass primary hit's bounce tree by certified walks too (cert_tree; ltb and c.ax its
 // LDS slot), instead of leaving the whole pixel to the exact path.
 // us_out: the primary walk's certified prefix (CertResult::us) for the exact path, -1 if none.
+// ak (LEAN): the launch's arguments, for the start's launch constants (KArgs::walk_b0 .. start_cell).
 template <bool TEX = false, bool TREE = false, int NL = kWgThreads, bool LEAN = false>
 __device__ __forceinline__ bool cert_pixel(const Ctx& c0, const Ray& ray0, f3& color_out, int max_refl = 0,
                                            int max_transp = 0, float* __restrict__ ltb = nullptr,
-                                           float* us_out = nullptr) {
+                                           float* us_out = nullptr, const KArgs* ak = nullptr) {
   const f3 P = ray0.pos, D = ray0.dir;
   int cx, cy, cz;
   CertStartK st;
@@ -1222,22 +1227,41 @@ __device__ __forceinline__ bool cert_pixel(const Ctx& c0, const Ray& ray0, f3& c
     // (D_b < 0 and P_b an integer: fast_path_ok excludes D_b = 0, where D_b < 0 and !(D_b > 0) differ),
     // puts that function, unchanged, behind one region.
     // (tests/test_cert_start_lit_forms.py: both forms over the sign octants and the edge positions)
+    //
+    // kSetupCell (KArgs::setup, wave-uniform; cert_launch_consts in vrt_context.cpp): the host has proved
+    // that every pixel's P_b of the launch lies strictly inside one cell c_b of the volume, at least 2^-9
+    // from its planes. Then floor(P_b) = c_b and floor(-P_b) = -c_b - 1 (P_b is no integer), so fl_b + 1
+    // is a select of two launch constants and the cell is c_b whatever the sign; the bounds hold; the plane
+    // tests hold (q + 1 rounds by at most 2^-14 at q < 1025, inside the margin); the trigger is false
+    // (fl_b != q_b). Only fast_path_ok(D) and the sign fold are left to the lane.
     const bool ux = D.x > 0.0f, uy = D.y > 0.0f, uz = D.z > 0.0f;
     st.Ps = mk(ux ? P.x : -P.x, uy ? P.y : -P.y, uz ? P.z : -P.z);
-    st.fl = mk(__builtin_floorf(st.Ps.x), __builtin_floorf(st.Ps.y), __builtin_floorf(st.Ps.z));
     st.mx = ux ? 0 : -1;
     st.my = uy ? 0 : -1;
     st.mz = uz ? 0 : -1;
-    cx = int(st.fl.x) ^ st.mx;
-    cy = int(st.fl.y) ^ st.my;
-    cz = int(st.fl.z) ^ st.mz;
-    bool ok = int(fast_path_ok(D)) & int(max(max(uint32_t(cx), uint32_t(cy)), uint32_t(cz)) < uint32_t(c0.n)) &
-              int(__builtin_floorf(st.Ps.x + 1.0f) == st.fl.x + 1.0f) &
-              int(__builtin_floorf(st.Ps.y + 1.0f) == st.fl.y + 1.0f) &
-              int(__builtin_floorf(st.Ps.z + 1.0f) == st.fl.z + 1.0f);
-    const bool on_plane = (int(!ux) & int(st.fl.x == st.Ps.x)) | (int(!uy) & int(st.fl.y == st.Ps.y)) |
-                          (int(!uz) & int(st.fl.z == st.Ps.z));
-    if (ok & on_plane) ok = start_layers_clear<false>(c0, P, D, cx, cy, cz, 0u);
+    st.b0 = ak->walk_b0;
+    st.U2 = ak->max_len2;  // (ray0.len = 0: the walk's U is max_len)
+    bool ok;
+    if ((ak->setup & kSetupCell) != 0u) {
+      st.fl1 = mk(ux ? ak->start_fl1[0] : ak->start_fl1[3], uy ? ak->start_fl1[1] : ak->start_fl1[4],
+                  uz ? ak->start_fl1[2] : ak->start_fl1[5]);
+      cx = ak->start_cell[0];
+      cy = ak->start_cell[1];
+      cz = ak->start_cell[2];
+      ok = fast_path_ok(D);
+    } else {
+      const f3 fl = mk(__builtin_floorf(st.Ps.x), __builtin_floorf(st.Ps.y), __builtin_floorf(st.Ps.z));
+      st.fl1 = mk(fl.x + 1.0f, fl.y + 1.0f, fl.z + 1.0f);
+      cx = int(fl.x) ^ st.mx;
+      cy = int(fl.y) ^ st.my;
+      cz = int(fl.z) ^ st.mz;
+      ok = int(fast_path_ok(D)) & int(max(max(uint32_t(cx), uint32_t(cy)), uint32_t(cz)) < uint32_t(c0.n)) &
+           int(__builtin_floorf(st.Ps.x + 1.0f) == st.fl1.x) & int(__builtin_floorf(st.Ps.y + 1.0f) == st.fl1.y) &
+           int(__builtin_floorf(st.Ps.z + 1.0f) == st.fl1.z);
+      const bool on_plane = (int(!ux) & int(fl.x == st.Ps.x)) | (int(!uy) & int(fl.y == st.Ps.y)) |
+                            (int(!uz) & int(fl.z == st.Ps.z));
+      if (ok & on_plane) ok = start_layers_clear<false>(c0, P, D, cx, cy, cz, 0u);
+    }
     if (!ok) { CERT_DIAG(0); return false; }
   } else {
     if (!fast_path_ok(D)) { CERT_DIAG(0); return false; }

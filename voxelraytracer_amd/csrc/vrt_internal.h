@@ -35,7 +35,7 @@ struct KArgs {
   // temporal epilogue (cur != nullptr): RGB8 store + temporal.glsl blend instead of float RGBA
   float alpha;
   // the vertex stage's division operands are in range for every pixel and frame of the launch
-  // (vertex_div_ranges_ok, vrt_context.cpp; primary_ray's div3_rn). In the padding before `prev`:
+  // (vertex_div_ranges_ok, vrt_context.cpp; primary_ray's div3_lean). In the padding before `prev`:
   // the layout is unchanged.
   uint32_t vdiv_ok;
   const uint32_t* prev;  // last filtered frame (RGBA8 words), band-local like the output
@@ -91,9 +91,30 @@ struct KArgs {
   int32_t sun_step[3];
   uint32_t sun_obase;
   float sun_l1, sun_q2, sun_b1, sun_g2;
+  // The certified pass's ray set-up and walk start (primary_ray<LEAN>, cert_pixel<LEAN>; no other kernel
+  // reads them), read where first used and dead before the primary walk's loop.
+  // Wave-uniform float work of the launch (setup_consts, filled where fn, width, height and max_len are;
+  // IEEE single in the kernel's order): fw = float(width), fh = float(height), half_n = fn * 0.5,
+  // walk_b0 = k24 (3 fn + 11) (cert_walk's b0), max_len2 = max_len + 2 (the primary walk's U + 2).
+  float fw, fh, half_n, walk_b0, max_len2;
+  // Per-launch proofs about the camera (cert_launch_consts, vrt_context.cpp; set by launch(), else 0):
+  // kSetupW: n4.w = wn and f4.w = wf for every pixel, both Markstein-safe; rcp_wn, rcp_wf = RN(1 / w).
+  // kSetupLen: every pixel's squared vdir length takes normalize3's rcp_newton(sqrt_fix(s)) with none
+  // of its range tests. kSetupCell: every pixel's start P lies strictly inside the cell start_cell (in
+  // [0, N)^3), away from its planes: start_fl1[b] = float(cell_b + 1) is floor(P_b) + 1 for a ray moving
+  // up axis b, start_fl1[3 + b] = float(-cell_b) is floor(-P_b) + 1 for one moving down.
+  uint32_t setup;
+  float wn, wf, rcp_wn, rcp_wf;
+  float start_fl1[6];
+  int32_t start_cell[3];
 };
+constexpr uint32_t kSetupW = 1u, kSetupLen = 2u, kSetupCell = 4u;
 // fills the sun_* constants above from a.sun_n and a.ostride (host, vrt_context.cpp)
 void sun_consts(KArgs& a);
+// fills fw .. max_len2 above from a.width, a.height, a.fn and a.max_len (host, vrt_context.cpp)
+void setup_consts(KArgs& a);
+// fills setup .. start_cell above from the launch's matrices, a.fn, a.n and a.vdiv_ok (host, vrt_context.cpp)
+void cert_launch_consts(KArgs& a);
 constexpr int kMaxBatch = 8;  // frames per launch (1 + the fb entries)
 constexpr int kWgThreads = 64 * kWgWaves;  // kWgWaves: vrt_tuning.h
 constexpr int kTileW = kWgWaves >= 2 ? 16 : 8;  // a workgroup's pixel tile: 16x16, 16x8 or 8x8

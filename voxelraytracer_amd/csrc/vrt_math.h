@@ -71,15 +71,18 @@ __device__ __forceinline__ float sqrt_rn(float s) { return sqrt_fix_ok(s) ? sqrt
 // normalize of an already normalised direction takes ~6 VALU instead of ~26.
 __device__ __forceinline__ float near_one_rsqrt(uint32_t b) {
   const uint32_t one = 0x3F800000u;
-  const uint32_t r = b >= one ? (b - one < 2u ? one : one - ((b - one) & ~1u))
-                              : one + (((((one - b) + 1u) >> 1) + 1u) >> 1);
+  // ((b - one) & ~1u is 0 for b - one < 2: s = 1 and 1 + 2^-23 give 1 without a select)
+  const uint32_t r = b >= one ? one - ((b - one) & ~1u) : one + (((((one - b) + 1u) >> 1) + 1u) >> 1);
   return __uint_as_float(r);
+}
+// normalize's factor RN(1 / RN(sqrt(s))) for any squared length s
+__device__ __forceinline__ float normalize3_scale(float s) {
+  const uint32_t b = __float_as_uint(s);
+  return b - (0x3F800000u - 1024u) <= 2048u ? near_one_rsqrt(b) : rcp_rn(sqrt_rn(s));
 }
 __device__ __forceinline__ f3 normalize3(f3 v) {
   const float s = v.x * v.x + v.y * v.y + v.z * v.z;
-  const uint32_t b = __float_as_uint(s);
-  const float inv = b - (0x3F800000u - 1024u) <= 2048u ? near_one_rsqrt(b) : rcp_rn(sqrt_rn(s));
-  return v * inv;
+  return v * normalize3_scale(s);
 }
 __device__ __forceinline__ float gsign(float x) { return x > 0.0f ? 1.0f : (x < 0.0f ? -1.0f : 0.0f); }
 __device__ __forceinline__ float gmin(float x, float y) { return y < x ? y : x; }
@@ -132,14 +135,16 @@ __device__ __forceinline__ bool zero_noise_exact_class(f3 d) {
 template <bool LEAN = false>
 __device__ __forceinline__ f3 randomize(f3 dir, f3 pos, float randomness, float seed) {
   f3 r = mk(0.0f, 0.0f, 0.0f);
+  f3 sum = dir;  // LEAN: on the fast path dir + r is dir bit for bit (above), an identity the compiler cannot fold
   if (!(randomness == 0.0f && (LEAN ? zero_noise_exact_class(dir) : zero_noise_exact(dir)))) {
     const f3 p = mk((pos.x + dir.x) + seed, (pos.y + dir.y) + seed, (pos.z + dir.z) + seed);
     const float dx = random4(p.x, p.y, p.z, 0.0f + seed);
     const float dy = random4(p.x, p.y, p.z, 0.5f + seed);
     const float dz = random4(p.x, p.y, p.z, 1.0f + seed);
     r = mk((dx + -0.5f) * randomness, (dy + -0.5f) * randomness, (dz + -0.5f) * randomness);
+    sum = dir + r;
   }
-  return normalize3(dir + r);
+  return normalize3(LEAN ? sum : dir + r);
 }
 
 // ------------------------------------------------------- materials (_COLOR_ONLY, :71-91) ----

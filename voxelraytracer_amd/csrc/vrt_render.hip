@@ -206,51 +206,93 @@ __device__ __forceinline__ bool markstein_safe(float x) {
   const float m = __builtin_fabsf(x);
   return m >= 0x1p-60f && m <= 0x1p60f;
 }
-// ranges_ok (KArgs::vdiv_ok, wave-uniform; read by the certified pass's instances only, LEAN): the
-// host has proved |x|, |y|, |z| <= 2^60 and |d| in [2^-60, 2^60] for every pixel of the launch, so
-// only the numerators' lower bound is left to the lane: the smallest |numerator| against 2^-60
-// (the values are finite, so the minimum drops no NaN). Each lane takes the same sequence either way.
-template <bool LEAN = false>
-__device__ __forceinline__ f3 div3_rn(float x, float y, float z, float d, bool ranges_ok = false) {
-  bool safe;
-  if constexpr (LEAN) {
-    // the same test in two parts: what the host may have proved (a wave-uniform branch around it;
-    // it also rejects NaN numerators, which the minimum drops), and the numerators' lower bound
-    bool rest = true;
-    if (!ranges_ok)
-      rest = int(__builtin_fabsf(x) <= 0x1p60f) & int(__builtin_fabsf(y) <= 0x1p60f) &
-             int(__builtin_fabsf(z) <= 0x1p60f) & int(markstein_safe(d));
-    safe = rest & (__builtin_fminf(__builtin_fminf(__builtin_fabsf(x), __builtin_fabsf(y)), __builtin_fabsf(z)) >=
-                   0x1p-60f);
-  } else {
-    safe = markstein_safe(x) && markstein_safe(y) && markstein_safe(z) && markstein_safe(d);
-  }
-  if (safe) {
+__device__ __forceinline__ f3 div3_rn(float x, float y, float z, float d) {
+  if (markstein_safe(x) && markstein_safe(y) && markstein_safe(z) && markstein_safe(d)) {
     const float r = rcp_newton(d);  // |d| in [2^-60, 2^60]: RN(1/d)
     return mk(div_rn(x, d, r), div_rn(y, d, r), div_rn(z, d, r));
   }
   return mk(x / d, y / d, z / d);
 }
+// The certified pass's form (LEAN) of the same test, in two parts: `rest`, what the host may have proved
+// for every pixel of the launch (|x|, |y|, |z| <= 2^60 and |d| in [2^-60, 2^60]: KArgs::vdiv_ok, or the
+// lane's own tests behind a wave-uniform branch; they also reject NaN numerators, which the minimum
+// drops), and the numerators' lower bound, the smallest |numerator| against 2^-60, which is left to the
+// lane. r: RN(1 / d) where d is Markstein-safe (rcp_newton(d), or the host's IEEE division of a
+// launch-constant d, KArgs::rcp_wn / rcp_wf: the same float). Each lane takes the same sequence either way.
+__device__ __forceinline__ f3 div3_lean(float x, float y, float z, float d, float r, bool rest) {
+  const bool safe = rest & (__builtin_fminf(__builtin_fminf(__builtin_fabsf(x), __builtin_fabsf(y)), __builtin_fabsf(z)) >=
+                            0x1p-60f);
+  if (safe) return mk(div_rn(x, d, r), div_rn(y, d, r), div_rn(z, d, r));
+  return mk(x / d, y / d, z / d);
+}
+__device__ __forceinline__ bool div3_lean_ranges(float x, float y, float z, float d) {
+  return int(__builtin_fabsf(x) <= 0x1p60f) & int(__builtin_fabsf(y) <= 0x1p60f) & int(__builtin_fabsf(z) <= 0x1p60f) &
+         int(markstein_safe(d));
+}
 
+// LEAN (the certified pass's instances): the quantities that are the same for every pixel of the launch come
+// from the host (KArgs::fw .. max_len2, and behind the wave-uniform flags of KArgs::setup, each a host proof
+// per launch, cert_launch_consts in vrt_context.cpp):
+//  - kSetupW: the w column is not formed: n4.w and f4.w are the launch's wn and wf bit for bit (the x and y
+//    terms are absorbed by the z term's rounding), their reciprocals the host's, and the tests of d proved;
+//  - kSetupLen: the squared length of vdir is inside normalize3's general range and away from its near-one
+//    window for every pixel: rcp_newton(sqrt_fix(s)) without the three range tests.
+// The same floats either way.
 template <bool LEAN = false>
 __device__ __forceinline__ Ray primary_ray(const KArgs& a, const float* __restrict__ inv_pv, const Ctx& c, int px,
                                            int py) {
   // (2 (p + 0.5)) / W with RN(1/W) from the host: the numerator is in (0, 2W), W <= 32768
-  const float ndx = div_rn(2.0f * (float(px) + 0.5f), float(a.width), a.rcp_w) - 1.0f;
-  const float ndy = div_rn(2.0f * (float(py) + 0.5f), float(a.height), a.rcp_h) - 1.0f;
+  const float ndx = div_rn(2.0f * (float(px) + 0.5f), LEAN ? a.fw : float(a.width), a.rcp_w) - 1.0f;
+  const float ndy = div_rn(2.0f * (float(py) + 0.5f), LEAN ? a.fh : float(a.height), a.rcp_h) - 1.0f;
   float n4[4], f4[4];
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
+  for (int i = 0; i < (LEAN ? 3 : 4); ++i) {
     const float base = inv_pv[0 * 4 + i] * ndx + inv_pv[1 * 4 + i] * ndy;
     n4[i] = (base + inv_pv[2 * 4 + i] * -1.0f) + inv_pv[3 * 4 + i] * 1.0f;
     f4[i] = (base + inv_pv[2 * 4 + i] * 1.0f) + inv_pv[3 * 4 + i] * 1.0f;
   }
-  const bool ranges_ok = LEAN && a.vdiv_ok != 0u;
-  const f3 vnear = div3_rn<LEAN>(n4[0], n4[1], n4[2], n4[3], ranges_ok);
-  const f3 vdir = div3_rn<LEAN>(f4[0], f4[1], f4[2], f4[3], ranges_ok) - vnear;
+  f3 vnear, vdir;
+  if constexpr (LEAN) {
+    float rn, rf;
+    bool rest_n = true, rest_f = true;
+    if ((a.setup & kSetupW) != 0u) {  // (implies vdiv_ok)
+      n4[3] = a.wn;
+      f4[3] = a.wf;
+      rn = a.rcp_wn;
+      rf = a.rcp_wf;
+    } else {
+      const float base = inv_pv[0 * 4 + 3] * ndx + inv_pv[1 * 4 + 3] * ndy;
+      n4[3] = (base + inv_pv[2 * 4 + 3] * -1.0f) + inv_pv[3 * 4 + 3] * 1.0f;
+      f4[3] = (base + inv_pv[2 * 4 + 3] * 1.0f) + inv_pv[3 * 4 + 3] * 1.0f;
+      if (a.vdiv_ok == 0u) {
+        rest_n = div3_lean_ranges(n4[0], n4[1], n4[2], n4[3]);
+        rest_f = div3_lean_ranges(f4[0], f4[1], f4[2], f4[3]);
+      }
+      rn = rcp_newton(n4[3]);  // RN(1 / d) where d is in range; not used elsewhere
+      rf = rcp_newton(f4[3]);
+    }
+    vnear = div3_lean(n4[0], n4[1], n4[2], n4[3], rn, rest_n);
+    vdir = div3_lean(f4[0], f4[1], f4[2], f4[3], rf, rest_f) - vnear;
+  } else {
+    vnear = div3_rn(n4[0], n4[1], n4[2], n4[3]);
+    vdir = div3_rn(f4[0], f4[1], f4[2], f4[3]) - vnear;
+  }
   Ray ray;
-  ray.pos = mk(vnear.x + c.fn * 0.5f, vnear.y + c.fn * 0.5f, vnear.z + c.fn * 0.5f);
-  ray.dir = randomize<LEAN>(normalize3(vdir), vnear, a.ray_noise, c.time);
+  const float half_n = LEAN ? a.half_n : c.fn * 0.5f;
+  ray.pos = mk(vnear.x + half_n, vnear.y + half_n, vnear.z + half_n);
+  f3 dir0;
+  if constexpr (LEAN) {
+    const float s = vdir.x * vdir.x + vdir.y * vdir.y + vdir.z * vdir.z;
+    float inv;
+    if ((a.setup & kSetupLen) != 0u)
+      inv = rcp_newton(sqrt_fix(s));
+    else
+      inv = normalize3_scale(s);
+    dir0 = vdir * inv;
+  } else {
+    dir0 = normalize3(vdir);
+  }
+  ray.dir = randomize<LEAN>(dir0, vnear, a.ray_noise, c.time);
   ray.len = 0.0f;
   ray.energy = 1.0f;
   ray.voxel = 0;
@@ -508,7 +550,7 @@ __global__ void __launch_bounds__(kWgThreads, TREE ? kTreeWaves : (DEFER ? kDefe
                             : mk(0.0f, 0.0f, 0.0f);
       need_exact = false;
     } else {
-      need_exact = CERT < 2 || !cert_pixel<TEX, TREE, kWgThreads, DEFER>(c, ray, color, a.max_refl, a.max_transp, tstk, &us);
+      need_exact = CERT < 2 || !cert_pixel<TEX, TREE, kWgThreads, DEFER>(c, ray, color, a.max_refl, a.max_transp, tstk, &us, &a);
     }
     STAMP_WAVE_CERT(need_exact);
     if constexpr (DEFER) {
