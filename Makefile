@@ -8,14 +8,18 @@ LIBDIR := voxelraytracer_amd/_lib
 # -fno-slp-vectorize: packed-FP32 (v_pk_*) ops take two issue slots on gfx950, no gain here
 HIPFLAGS := -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -ffp-contract=off \
             -fhip-fp32-correctly-rounded-divide-sqrt -fno-slp-vectorize -Iinclude -Wall
-SRC := voxelraytracer_amd/csrc/vrt_render.hip voxelraytracer_amd/csrc/vrt_context.cpp \
-       voxelraytracer_amd/csrc/vrt_host.cpp
 CSRC := voxelraytracer_amd/csrc
-HDR := include/vrt.h $(CSRC)/vrt_internal.h $(CSRC)/vrt_tuning.h $(CSRC)/vrt_diag.h $(CSRC)/vrt_math.h \
+# the C-ABI context, one file per concern; vrt_launch_consts.cpp and vrt_bands.cpp are plain
+# host arithmetic (no HIP or RCCL call) but take the same flags: -ffp-contract=off is part of their contract
+SRC := $(CSRC)/vrt_render.hip $(CSRC)/vrt_context.cpp $(CSRC)/vrt_launch_consts.cpp $(CSRC)/vrt_bands.cpp \
+       $(CSRC)/vrt_launch.cpp $(CSRC)/vrt_volume.cpp $(CSRC)/vrt_frames.cpp $(CSRC)/vrt_band_api.cpp \
+       $(CSRC)/vrt_queries.cpp $(CSRC)/vrt_host.cpp
+HDR := include/vrt.h $(CSRC)/vrt_internal.h $(CSRC)/vrt_context.h $(CSRC)/vrt_bands.h \
+       $(CSRC)/vrt_tuning.h $(CSRC)/vrt_diag.h $(CSRC)/vrt_math.h \
        $(CSRC)/vrt_walk.h $(CSRC)/vrt_cert.h $(CSRC)/vrt_aux_kernels.h \
        $(CSRC)/vrt_skipfield_kernels.h $(CSRC)/vrt_query_kernels.h $(CSRC)/vrt_trace_kernels.h \
        $(CSRC)/vrt_ids_kernels.h $(CSRC)/vrt_reproject_kernels.h
-# RCCL: volume broadcast and the frame gather of multi-device contexts (vrt_context.cpp)
+# RCCL: volume broadcast and the frame gather of multi-device contexts (vrt_volume.cpp, vrt_frames.cpp)
 LIBS := -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
 
 all: $(LIBDIR)/libvrt.so oracle app

@@ -1,5 +1,5 @@
 """The certified pass's launch constants (KArgs::setup and the fields behind its flags, KArgs::fw .. max_len2;
-cert_launch_consts and setup_consts in csrc/vrt_context.cpp, through the library's host-only test hook)
+cert_launch_consts and setup_consts in csrc/vrt_launch_consts.cpp, through the library's host-only test hook)
 against a NumPy float32 restatement of primary_ray's vertex stage and start (csrc/vrt_render.hip) over
 every pixel of small frames and the corner and centre pixels of large ones.
 

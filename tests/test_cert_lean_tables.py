@@ -1,5 +1,5 @@
 """CPU truth tables of the certified pass's lean forms (vrt_cert.h cert_walk<.., LEAN>, vrt_math.h
-zero_noise_exact_class, vrt_render.hip div3_rn<LEAN>, vrt_context.cpp vertex_div_ranges_ok): each
+zero_noise_exact_class, vrt_render.hip div3_rn<LEAN>, vrt_launch_consts.cpp vertex_div_ranges_ok): each
 lean form is restated in NumPy float32 beside the form it replaces and compared over the special
 values (+-0, NaN, +-inf, denormals, the thresholds 2^-64, 2^-60, 2^60, 1e4 and their neighbours)
 and a few million random bit patterns. v_min3_f32 / v_max3_f32 are np.fmin / np.fmax (a NaN operand

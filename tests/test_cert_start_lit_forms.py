@@ -4,7 +4,7 @@ two walks (csrc/vrt_cert.h) beside the forms they replace:
    sign-folded cell int(floor(s P)) ^ m with the plane test floor(q + 1) == floor(q) + 1, and
    start_layers_clear's per-axis entry condition against the on-plane trigger;
  - cert_shade_hit's lit term: dot3 / reflect3 / dot3 on the face normal against the axis form;
- - the sun's launch constants (KArgs::sun_*, sun_consts in vrt_context.cpp, through the library's test
+ - the sun's launch constants (KArgs::sun_*, sun_consts in vrt_launch_consts.cpp, through the library's test
    hook) against the kernel's expressions.
 float -> int is v_cvt_i32_f32: NaN gives 0, values beyond the range saturate."""
 import ctypes as C

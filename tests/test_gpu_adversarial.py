@@ -165,7 +165,7 @@ def test_stats_free_frames_equal_the_exact_frame(built, name, n):
 @pytest.mark.parametrize("name,n", CASES)
 def test_automatic_mode_follows_the_glass_share(built, name, n):
     """vrt_set_certified's automatic mode (0) certifies unless glass (byte 2) makes up more than 1 / 8 of the
-    non-empty voxels: derive_glass_flags (csrc/vrt_context.cpp) keeps it on while glass * 8 <= non_empty.
+    non-empty voxels: derive_glass_flags (csrc/vrt_volume.cpp) keeps it on while glass * 8 <= non_empty.
     `empty` has zero non-empty voxels: 0 * 8 <= 0 holds, so certified() is True; `glass_solid` is all
     glass: False. With certified bounce trees at their default (1) a glass-heavy volume stays certified
     through the trees, so certified() is True for every volume. The frames are equal in either mode."""

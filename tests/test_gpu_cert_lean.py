@@ -105,7 +105,7 @@ def test_frame_shapes_bands_and_batches(built, scene, n, w, h):
 
 
 def vertex_div_ranges_ok(inv_pv):
-    """vrt_context.cpp's bound, restated: with |ndx|, |ndy| <= 1 component i of n4 and f4 is at most
+    """vrt_launch_consts.cpp's bound, restated: with |ndx|, |ndy| <= 1 component i of n4 and f4 is at most
     S_i = sum_r |m_ri| in magnitude and the denominators at least |m_33 -+ m_23| - |m_03| - |m_13|;
     the kernel's float evaluation is allowed 2^-20 S_i; bounds 2^59 and 2^-59."""
     m = np.asarray(inv_pv, np.float64)

@@ -271,6 +271,20 @@ def test_counts_and_untouched_tail(built, mode):
         r.cast_rays_async(0, 0, 0, mode)
 
 
+def test_staging_grows_and_is_reused(built):
+    """One renderer's casts of 5, 4 097, 9 000 and 5 rays: the synchronous staging's first allocation (its
+    4 096-record floor), two growths, then the larger buffers reused for a short list."""
+    vox, rays = scene_rays("terrain")
+    want = oracle_nearest("terrain")
+    with vrt.Renderer(0) as r:
+        r.upload_volume(vox, N)
+        for count in (5, 4097, 9000, 5):
+            idx = np.arange(count) % COUNT
+            hits = r.cast_rays(rays[idx], "nearest")
+            assert hits.shape == (count,)
+            assert_nearest_matches(hits, {key: v[idx] for key, v in want.items()}, vox, rays[idx])
+
+
 def test_async_on_a_torch_stream_equals_the_synchronous_cast(built):
     import torch
 

@@ -134,6 +134,24 @@ def test_frame_shapes(built, w, h, layout):
         assert np.array_equal(np.isposinf(depth), picks["voxel_index"] < 0)
 
 
+def test_staging_grows_and_is_reused(built):
+    """One renderer's frames of 16x8, 64x48 and 16x8 again, with and without depth: the synchronous
+    staging's first allocation, its growth, and the larger buffers reused for the small frame."""
+    p = params()
+    with vrt.Renderer(0) as r:
+        r.upload_volume(scene("refraction"), N)
+        for w, h in ((16, 8), (64, 48), (16, 8)):
+            cam = vrt.make_camera(w, h)
+            ids, depth = r.render_ids(cam, p)
+            ids_only, none = r.render_ids(cam, p, want_depth=False)
+            assert r.ids_deferred()[0] == w * h
+            picks = pick_frame(r, cam, p)
+            assert ids.shape == depth.shape == (h, w) and none is None
+            assert_ids_equal_pick(ids, picks, (w, h))
+            assert ids.tobytes() == ids_only.tobytes()
+            assert np.array_equal(np.isposinf(depth), picks["voxel_index"] < 0)
+
+
 @pytest.mark.parametrize("layout", [8, 1])
 def test_async_band_with_pitch_on_a_torch_stream(built, layout):
     import torch

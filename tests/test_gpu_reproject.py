@@ -353,6 +353,26 @@ def test_resets_and_the_plain_history(built):
             assert np.array_equal(a, b), f
 
 
+def test_staging_grows_and_is_reused(built):
+    """One renderer's frames of 16x8 twice, 96x54 twice and 16x8 twice: the staging's first allocation, its
+    growth and the larger buffers reused. Every first frame of a size has no history (it is the raw frame);
+    every second one is the frame a fresh renderer gives after the same two calls."""
+    ps = [ref.params(0.0, float(t), sun_dir=vrt.sun_dir(40.0 + t)) for t in range(1, 7)]
+    with vrt.Renderer(0) as r, vrt.Renderer(0) as plain:
+        r.upload_volume(ref.scene("refraction"), N)
+        plain.upload_volume(ref.scene("refraction"), N)
+        for i, (w, h) in enumerate(((16, 8), (W, H), (16, 8))):
+            cam, p0, p1 = ref.camera("A", w, h), ps[2 * i], ps[2 * i + 1]
+            first = r.render_frame_reprojected(cam, p0, ALPHA)
+            second = r.render_frame_reprojected(cam, p1, ALPHA)
+            assert np.array_equal(first, plain.render_frame(cam, p0, 1.0)[0]), (w, h)
+            assert not np.array_equal(second, plain.render_frame(cam, p1, 1.0)[0]), (w, h)
+            with vrt.Renderer(0) as fresh:
+                fresh.upload_volume(ref.scene("refraction"), N)
+                fresh.render_frame_reprojected(cam, p0, ALPHA)
+                assert np.array_equal(second, fresh.render_frame_reprojected(cam, p1, ALPHA)), (w, h)
+
+
 # ---- errors, timing --------------------------------------------------------------------------------
 
 def test_errors_leave_the_outputs_untouched(built):

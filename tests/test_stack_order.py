@@ -78,7 +78,7 @@ def test_kernel_stack_order_matches_reference(R, T):
 
 
 def test_abi_capacity_never_drops():
-    """cap = R + T + 1 (vrt_context.cpp validation): STACK_FULL cannot be set."""
+    """cap = R + T + 1 (vrt_context.cpp check_render_args): STACK_FULL cannot be set."""
     for seed in range(300):
         for R, T in [(4, 4), (8, 8), (12, 4)]:
             assert reference_order(seed, R + T + 1, R, T)[1] == 0

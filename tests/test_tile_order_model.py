@@ -1,5 +1,5 @@
 """CPU model of the heavy-first tile order's bookkeeping (vrt_render.hip ordered_tile /
-order_record, vrt_context.cpp tile_order_begin), checked over many launches with random heavy
+order_record, vrt_launch.cpp launch_state_begin), checked over many launches with random heavy
 patterns and random completion orders: every tile is rendered exactly once per launch, and every
 slot keeps its tile's residue mod 8 (the XCD the tile rendered on before). The GPU side of the
 same property is tests/test_gpu_tile_order.py (in-place alpha 0.5 frames, where a tile rendered

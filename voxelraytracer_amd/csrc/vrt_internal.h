@@ -1,5 +1,5 @@
 // vrt_internal.h — the interface between the kernels (vrt_render.hip and its headers) and the C-ABI context
-// (vrt_context.cpp). Not installed; include/vrt.h is the public boundary.
+// (vrt_context.h and the vrt_*.cpp files around it). Not installed; include/vrt.h is the public boundary.
 #ifndef VRT_INTERNAL_H
 #define VRT_INTERNAL_H
 
@@ -35,7 +35,7 @@ struct KArgs {
   // temporal epilogue (cur != nullptr): RGB8 store + temporal.glsl blend instead of float RGBA
   float alpha;
   // the vertex stage's division operands are in range for every pixel and frame of the launch
-  // (vertex_div_ranges_ok, vrt_context.cpp; primary_ray's div3_lean). In the padding before `prev`:
+  // (vertex_div_ranges_ok, vrt_launch_consts.cpp; primary_ray's div3_lean). In the padding before `prev`:
   // the layout is unchanged.
   uint32_t vdiv_ok;
   const uint32_t* prev;  // last filtered frame (RGBA8 words), band-local like the output
@@ -97,7 +97,7 @@ struct KArgs {
   // IEEE single in the kernel's order): fw = float(width), fh = float(height), half_n = fn * 0.5,
   // walk_b0 = k24 (3 fn + 11) (cert_walk's b0), max_len2 = max_len + 2 (the primary walk's U + 2).
   float fw, fh, half_n, walk_b0, max_len2;
-  // Per-launch proofs about the camera (cert_launch_consts, vrt_context.cpp; set by launch(), else 0):
+  // Per-launch proofs about the camera (cert_launch_consts, vrt_launch_consts.cpp; set by launch(), else 0):
   // kSetupW: n4.w = wn and f4.w = wf for every pixel, both Markstein-safe; rcp_wn, rcp_wf = RN(1 / w).
   // kSetupLen: every pixel's squared vdir length takes normalize3's rcp_newton(sqrt_fix(s)) with none
   // of its range tests. kSetupCell: every pixel's start P lies strictly inside the cell start_cell (in
@@ -109,11 +109,16 @@ struct KArgs {
   int32_t start_cell[3];
 };
 constexpr uint32_t kSetupW = 1u, kSetupLen = 2u, kSetupCell = 4u;
-// fills the sun_* constants above from a.sun_n and a.ostride (host, vrt_context.cpp)
+// The launch proofs (host, vrt_launch_consts.cpp: arithmetic only, built without contraction):
+// fills a.sun_n and a.sun_rcp from u_SunDir
+void fill_sun(KArgs& a, const float* sun_dir);
+// fills the sun_* constants above from a.sun_n and a.ostride
 void sun_consts(KArgs& a);
-// fills fw .. max_len2 above from a.width, a.height, a.fn and a.max_len (host, vrt_context.cpp)
+// fills fw .. max_len2 above from a.width, a.height, a.fn and a.max_len
 void setup_consts(KArgs& a);
-// fills setup .. start_cell above from the launch's matrices, a.fn, a.n and a.vdiv_ok (host, vrt_context.cpp)
+// KArgs::vdiv_ok of one camera matrix
+bool vertex_div_ranges_ok(const float* inv_pv);
+// fills setup .. start_cell above from the launch's matrices, a.fn, a.n and a.vdiv_ok
 void cert_launch_consts(KArgs& a);
 constexpr int kMaxBatch = 8;  // frames per launch (1 + the fb entries)
 constexpr int kWgThreads = 64 * kWgWaves;  // kWgWaves: vrt_tuning.h

@@ -1,0 +1,397 @@
+// vrt_queries.cpp — queries on the resident volume, all on the first device: ray casts and pixel picks, shaded
+// ray and pixel traces, the ID and depth pass, and the reprojected temporal filter (vrt_context.h).
+#include <algorithm>
+#include <cstring>
+
+#include "vrt_context.h"
+
+using namespace vrt;
+
+extern "C" {
+
+// ---- ray queries (vrt_query_kernels.h) ---------------------------------------------------------
+
+// Arguments shared by the casts. Device buffers (the kernel's 16-byte loads and stores) must be
+// 16-byte aligned; host buffers are only copied.
+static int check_cast(vrt_ctx* ctx, const void* rays, int64_t count, int32_t mode, const void* hits, bool device) {
+  if (!ctx->sh[0].d_vox_pad) return fail(ctx, VRT_ERR_NO_VOLUME, "no volume uploaded");
+  if (count < 0 || count > (int64_t(1) << 30)) return fail(ctx, VRT_ERR_INVALID, "ray count must be in [0, 2^30]");
+  if (mode != VRT_CAST_NEAREST && mode != VRT_CAST_OCCLUSION) return fail(ctx, VRT_ERR_INVALID, "unknown cast mode");
+  if (count > 0 && (!rays || !hits)) return fail(ctx, VRT_ERR_INVALID, "null ray or hit buffer");
+  if (device && count > 0 && ((reinterpret_cast<uintptr_t>(rays) | reinterpret_cast<uintptr_t>(hits)) & 15u) != 0)
+    return fail(ctx, VRT_ERR_INVALID, "device ray and hit buffers must be 16-byte aligned");
+  return VRT_OK;
+}
+
+// The argument block of a cast: ray_query_kernel reads the volume's fields only
+static vrt::KArgs cast_args(const Shard& s) {
+  vrt::KArgs a{};
+  a.n = s.n;
+  a.fn = float(s.n);
+  a.ostride = octant_stride(s);
+  return a;
+}
+
+// The synchronous queries' staging on the first device (the current one): `records` of 32 bytes in
+// and out. The queries are synchronous, so no launch still reads buffers that are replaced here.
+static int ensure_query_stage(vrt_ctx* ctx, size_t records) {
+  static_assert(sizeof(vrt_ray) == 32 && sizeof(vrt_ray_hit) == 32, "query records are 32 bytes");
+  if (ctx->d_query_in.cap >= records) return VRT_OK;
+  const size_t cap = std::max<size_t>(std::max(records, 2 * ctx->d_query_in.cap), 4096);
+  if (!stage_alloc_all(cap, ctx->d_query_in, ctx->d_query_out))
+    return fail(ctx, VRT_ERR_OOM, "hipMalloc ray-query staging");
+  return VRT_OK;
+}
+
+// `in` (host, in_bytes) to the staging, one query launch over `count` queries (shaded: launch_ray_trace
+// of kind kTraceRays / kTracePixels, else launch_ray_query), the 32-byte records back to `out` (host); waits
+static int run_query_staged(vrt_ctx* ctx, const vrt::KArgs& a, int32_t kind, bool shaded, const void* in,
+                            size_t in_bytes, size_t count, void* out) {
+  static_assert(sizeof(vrt_ray_color) == sizeof(vrt_ray_hit), "one staging for both record types");
+  DeviceGuard guard;
+  Shard& s = ctx->sh[0];
+  VRT_HIP(ctx, hipSetDevice(s.device));
+  const int st = ensure_query_stage(ctx, count);
+  if (st != VRT_OK) return st;
+  hipStream_t qs = main_stream(s);
+  VRT_HIP(ctx, hipMemcpyAsync(ctx->d_query_in.p, in, in_bytes, hipMemcpyHostToDevice, qs));
+  hipEvent_t eb, ee;
+  launch_timing_events(ctx, eb, ee);
+  if (shaded)
+    vrt::launch_ray_trace(a, kind, s.d_vox_pad, ctx->d_query_in.p, uint32_t(count),
+                          reinterpret_cast<vrt_ray_color*>(ctx->d_query_out.p), qs, eb, ee);
+  else
+    vrt::launch_ray_query(a, kind, s.d_vox_pad, ctx->d_query_in.p, uint32_t(count), ctx->d_query_out.p, qs, eb, ee);
+  VRT_HIP(ctx, hipGetLastError());
+  VRT_HIP(ctx, hipMemcpyAsync(out, ctx->d_query_out.p, count * sizeof(vrt_ray_hit), hipMemcpyDeviceToHost, qs));
+  VRT_HIP(ctx, hipStreamSynchronize(qs));
+  return VRT_OK;
+}
+
+int vrt_cast_rays_async(vrt_ctx* ctx, const vrt_ray* d_rays, int64_t count, int32_t mode, vrt_ray_hit* d_hits,
+                        void* hip_stream) {
+  if (!ctx) return VRT_ERR_INVALID;
+  const int st = check_cast(ctx, d_rays, count, mode, d_hits, true);
+  if (st != VRT_OK || count == 0) return st;
+  Shard& s = ctx->sh[0];
+  hipEvent_t eb, ee;
+  launch_timing_events(ctx, eb, ee);
+  vrt::launch_ray_query(cast_args(s), mode, s.d_vox_pad, d_rays, uint32_t(count), d_hits,
+                        static_cast<hipStream_t>(hip_stream), eb, ee);
+  VRT_HIP(ctx, hipGetLastError());
+  return VRT_OK;
+}
+
+int vrt_cast_rays(vrt_ctx* ctx, const vrt_ray* rays, int64_t count, int32_t mode, vrt_ray_hit* hits) {
+  if (!ctx) return VRT_ERR_INVALID;
+  const int st = check_cast(ctx, rays, count, mode, hits, false);
+  if (st != VRT_OK || count == 0) return st;
+  return run_query_staged(ctx, cast_args(ctx->sh[0]), mode, false, rays, size_t(count) * sizeof(vrt_ray),
+                          size_t(count), hits);
+}
+
+int vrt_pick_pixels(vrt_ctx* ctx, const vrt_camera* cam, const vrt_params* p, const int32_t* pixels, int32_t count,
+                    vrt_ray_hit* hits) {
+  if (!ctx) return VRT_ERR_INVALID;
+  if (!cam || !p) return fail(ctx, VRT_ERR_INVALID, "null camera or params");
+  Shard& s = ctx->sh[0];
+  if (!s.d_vox_pad) return fail(ctx, VRT_ERR_NO_VOLUME, "no volume uploaded");
+  if (const int st = check_image(ctx, cam); st != VRT_OK) return st;
+  if (count < 0) return fail(ctx, VRT_ERR_INVALID, "pixel count must be >= 0");
+  if (count == 0) return VRT_OK;
+  if (!pixels || !hits) return fail(ctx, VRT_ERR_INVALID, "null pixel or hit buffer");
+  if (const int st = check_pixel_list(ctx, cam, pixels, count); st != VRT_OK) return st;
+  // the frame's argument block, as the frame launches fill it (launch): primary_ray reads it
+  vrt::KArgs a = make_args(ctx, s, cam, p, 0, cam->height, 1);
+  return run_query_staged(ctx, a, vrt::kQueryPick, false, pixels, size_t(count) * 2 * sizeof(int32_t), size_t(count),
+                          hits);
+}
+
+// ---- ID and depth pass (vrt_ids_kernels.h) -----------------------------------------------------
+
+// Arguments shared by vrt_render_ids*, in the pick's order. rows / pitch: the band (the synchronous form
+// passes the whole frame's); device: the buffers' alignment is checked (the kernels' 8- and 4-byte stores)
+static int check_ids(vrt_ctx* ctx, const vrt_camera* cam, const vrt_params* p, int32_t row0, int32_t rows,
+                     int64_t pitch, const void* ids, const void* depth, bool device) {
+  if (!cam || !p) return fail(ctx, VRT_ERR_INVALID, "null camera or params");
+  if (!ctx->sh[0].d_vox_pad) return fail(ctx, VRT_ERR_NO_VOLUME, "no volume uploaded");
+  if (const int st = check_image(ctx, cam); st != VRT_OK) return st;
+  if (rows < 0 || row0 < 0 || int64_t(row0) + rows > cam->height)
+    return fail(ctx, VRT_ERR_INVALID, "row band outside the image");
+  if (pitch < cam->width) return fail(ctx, VRT_ERR_INVALID, "row pitch must be >= the image width");
+  if (!ids) return fail(ctx, VRT_ERR_INVALID, "null id buffer");
+  if (device && ((reinterpret_cast<uintptr_t>(ids) & 7u) != 0 || (reinterpret_cast<uintptr_t>(depth) & 3u) != 0))
+    return fail(ctx, VRT_ERR_INVALID, "device id buffer must be 8-byte aligned, depth buffer 4-byte aligned");
+  return VRT_OK;
+}
+
+// One ID pass over rows [row0, row0 + rows) (rows >= 1) on `st`: one launch of the exact ID kernel, no
+// allocation, no host synchronisation
+static int enqueue_ids(vrt_ctx* ctx, const vrt_camera* cam, const vrt_params* p, int32_t row0, int32_t rows,
+                       int32_t pitch, vrt_pixel_id* d_ids, float* d_depth, hipStream_t st) {
+  Shard& s = ctx->sh[0];
+  // the frame's argument block, as the frame launches fill it (launch): primary_ray reads it
+  vrt::KArgs a = make_args(ctx, s, cam, p, row0, rows, 1);
+  a.pitch = pitch;
+  hipEvent_t eb, ee;
+  launch_timing_events(ctx, eb, ee);
+  vrt::launch_render_ids(a, s.d_vox_pad, d_ids, d_depth, st, eb, ee);
+  VRT_HIP(ctx, hipGetLastError());
+  return VRT_OK;
+}
+
+int vrt_render_ids_async(vrt_ctx* ctx, const vrt_camera* cam, const vrt_params* p, int32_t row0, int32_t rows,
+                         int32_t pitch, vrt_pixel_id* d_ids, float* d_depth, void* hip_stream) {
+  if (!ctx) return VRT_ERR_INVALID;
+  const int st = check_ids(ctx, cam, p, row0, rows, pitch, d_ids, d_depth, true);
+  if (st != VRT_OK || rows == 0) return st;
+  return enqueue_ids(ctx, cam, p, row0, rows, pitch, d_ids, d_depth, static_cast<hipStream_t>(hip_stream));
+}
+
+int vrt_render_ids(vrt_ctx* ctx, const vrt_camera* cam, const vrt_params* p, vrt_pixel_id* ids, float* depth) {
+  if (!ctx) return VRT_ERR_INVALID;
+  int st = check_ids(ctx, cam, p, 0, cam ? cam->height : 0, cam ? cam->width : 0, ids, depth, false);
+  if (st != VRT_OK) return st;
+  DeviceGuard guard;
+  Shard& s = ctx->sh[0];
+  VRT_HIP(ctx, hipSetDevice(s.device));
+  const size_t px = size_t(cam->width) * size_t(cam->height);
+  // the staging: synchronous calls only, so no launch still writes buffers that are replaced here
+  if (ctx->d_ids_stage.cap < px && !stage_alloc_all(px, ctx->d_ids_stage, ctx->d_depth_stage))
+    return fail(ctx, VRT_ERR_OOM, "hipMalloc ID pass staging");
+  hipStream_t qs = main_stream(s);
+  st = enqueue_ids(ctx, cam, p, 0, cam->height, cam->width, ctx->d_ids_stage.p, depth ? ctx->d_depth_stage.p : nullptr, qs);
+  if (st != VRT_OK) return st;
+  VRT_HIP(ctx, hipMemcpyAsync(ids, ctx->d_ids_stage.p, px * sizeof(vrt_pixel_id), hipMemcpyDeviceToHost, qs));
+  if (depth) VRT_HIP(ctx, hipMemcpyAsync(depth, ctx->d_depth_stage.p, px * sizeof(float), hipMemcpyDeviceToHost, qs));
+  VRT_HIP(ctx, hipStreamSynchronize(qs));
+  // no certified ID kernel yet: every pixel takes the exact kernel, on every layout
+  ctx->ids_pixels = px;
+  ctx->ids_deferred = px;
+  return VRT_OK;
+}
+
+int vrt_ids_deferred(vrt_ctx* ctx, uint64_t* pixels, uint64_t* deferred) {
+  if (!ctx) return VRT_ERR_INVALID;
+  if (!pixels || !deferred) return fail(ctx, VRT_ERR_INVALID, "null output");
+  *pixels = ctx->ids_pixels;
+  *deferred = ctx->ids_deferred;
+  return VRT_OK;
+}
+
+// ---- reprojected temporal filter (vrt_reproject_kernels.h) --------------------------------------
+
+// What vrt_reproject_temporal_async checks beyond check_ids (which takes the band's ids and depth)
+static int check_reproject(vrt_ctx* ctx, const vrt_camera* cam, const float* prev_pv, int32_t prev_pitch,
+                           const void* raw, const void* depth, const void* prev, const void* prev_ids, const void* out,
+                           const void* src) {
+  if (!prev_pv) return fail(ctx, VRT_ERR_INVALID, "null previous matrix");
+  if (!raw || !depth || !out) return fail(ctx, VRT_ERR_INVALID, "null raw, depth or output buffer");
+  if (prev_pitch < cam->width) return fail(ctx, VRT_ERR_INVALID, "previous row pitch must be >= the image width");
+  if ((prev == nullptr) != (prev_ids == nullptr))
+    return fail(ctx, VRT_ERR_INVALID, "the previous frame and its id buffer are given together or not at all");
+  if (prev && out == prev) return fail(ctx, VRT_ERR_INVALID, "the output must not alias the previous frame");
+  const uintptr_t words = reinterpret_cast<uintptr_t>(raw) | reinterpret_cast<uintptr_t>(prev) |
+                          reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(src);
+  if ((words & 3u) != 0 || (reinterpret_cast<uintptr_t>(prev_ids) & 7u) != 0)
+    return fail(ctx, VRT_ERR_INVALID, "device id buffers must be 8-byte aligned, the other buffers 4-byte aligned");
+  return VRT_OK;
+}
+
+// One reprojection launch over rows [row0, row0 + rows) (rows >= 1) on `st`: no allocation, no host
+// synchronisation. eb / ee: the launch's device timestamps (optional)
+static int enqueue_reproject(vrt_ctx* ctx, const vrt_camera* cam, const vrt_params* p, const float* prev_pv, float alpha,
+                             int32_t row0, int32_t rows, int32_t pitch, const uint32_t* d_raw, const vrt_pixel_id* d_ids,
+                             const float* d_depth, const uint32_t* d_prev, const vrt_pixel_id* d_prev_ids,
+                             int32_t prev_pitch, uint32_t* d_out, int32_t* d_src, hipStream_t st, hipEvent_t eb,
+                             hipEvent_t ee) {
+  Shard& s = ctx->sh[0];
+  // the frame's argument block, as enqueue_ids fills it: primary_ray reads it
+  vrt::KArgs a = make_args(ctx, s, cam, p, row0, rows, 1);
+  a.pitch = pitch;
+  vrt::ReprojArgs r;
+  std::memcpy(r.pv, prev_pv, sizeof(r.pv));
+  r.alpha = alpha;
+  r.prev_pitch = prev_pitch;
+  r.raw = d_raw;
+  r.ids = reinterpret_cast<const uint2*>(d_ids);
+  r.depth = d_depth;
+  r.prev = d_prev;
+  r.prev_ids = reinterpret_cast<const uint2*>(d_prev_ids);
+  r.out = d_out;
+  r.src = d_src;
+  vrt::launch_reproject(a, r, st, eb, ee);
+  VRT_HIP(ctx, hipGetLastError());
+  return VRT_OK;
+}
+
+int vrt_reproject_temporal_async(vrt_ctx* ctx, const vrt_camera* cam, const vrt_params* p, const float prev_pv[16],
+                                 float alpha, int32_t row0, int32_t rows, int32_t pitch, const uint32_t* d_raw_rgba8,
+                                 const vrt_pixel_id* d_ids, const float* d_depth, const uint32_t* d_prev_rgba8,
+                                 const vrt_pixel_id* d_prev_ids, int32_t prev_pitch, uint32_t* d_out_rgba8,
+                                 int32_t* d_src, void* hip_stream) {
+  if (!ctx) return VRT_ERR_INVALID;
+  int st = check_ids(ctx, cam, p, row0, rows, pitch, d_ids, d_depth, true);
+  if (st != VRT_OK) return st;
+  st = check_reproject(ctx, cam, prev_pv, prev_pitch, d_raw_rgba8, d_depth, d_prev_rgba8, d_prev_ids, d_out_rgba8,
+                       d_src);
+  if (st != VRT_OK || rows == 0) return st;
+  hipEvent_t eb, ee;
+  launch_timing_events(ctx, eb, ee);
+  return enqueue_reproject(ctx, cam, p, prev_pv, alpha, row0, rows, pitch, d_raw_rgba8, d_ids, d_depth, d_prev_rgba8,
+                           d_prev_ids, prev_pitch, d_out_rgba8, d_src, static_cast<hipStream_t>(hip_stream), eb, ee);
+}
+
+// The staging of vrt_render_frame_reprojected on the first device (the current one), for frames of w x h:
+// the raw frame, the depth, and ping-pong filtered frames and ID buffers. Synchronous calls only, so no
+// launch still uses buffers that are replaced here. A new size drops the history.
+static int ensure_reproject_stage(vrt_ctx* ctx, int32_t w, int32_t h) {
+  if (w == ctx->rp_w && h == ctx->rp_h) return VRT_OK;
+  const size_t px = size_t(w) * size_t(h);
+  ctx->rp_w = ctx->rp_h = 0;
+  ctx->rp_valid = false;
+  if (ctx->d_rp_raw.cap < px && !stage_alloc_all(px, ctx->d_rp_raw, ctx->d_rp_depth, ctx->d_rp_out[0], ctx->d_rp_out[1],
+                                                 ctx->d_rp_ids[0], ctx->d_rp_ids[1]))
+    return fail(ctx, VRT_ERR_OOM, "hipMalloc reprojected-frame staging");
+  if (!ctx->ev_rp_beg) VRT_HIP(ctx, hipEventCreate(&ctx->ev_rp_beg));
+  if (!ctx->ev_rp_end) VRT_HIP(ctx, hipEventCreate(&ctx->ev_rp_end));
+  ctx->rp_w = w;
+  ctx->rp_h = h;
+  return VRT_OK;
+}
+
+int vrt_render_frame_reprojected(vrt_ctx* ctx, const vrt_camera* cam, const vrt_params* p, float alpha,
+                                 uint8_t* out_rgba8, vrt_stats* stats) {
+  if (!ctx) return VRT_ERR_INVALID;
+  int st = check_render_args(ctx, cam, p);
+  if (st != VRT_OK) return st;
+  if (!out_rgba8) return fail(ctx, VRT_ERR_INVALID, "null output");
+  if (stats && (stats->request & VRT_STATS_COUNTERS))
+    return fail(ctx, VRT_ERR_UNSUPPORTED, "vrt_render_frame_reprojected does not count");
+  DeviceGuard guard;
+  Shard& s = ctx->sh[0];
+  VRT_HIP(ctx, hipSetDevice(s.device));
+  const int32_t w = cam->width, h = cam->height;
+  if ((st = ensure_reproject_stage(ctx, w, h)) != VRT_OK) return st;
+  const size_t bytes = size_t(w) * size_t(h) * 4;
+  if ((st = ensure_stage(ctx, bytes)) != VRT_OK) return st;
+  hipStream_t ms = main_stream(s);
+  const int cur = ctx->rp_cur ^ 1, prev = ctx->rp_cur;
+  // 1. the quantised ray-traced frame: the temporal band path at u_Alpha = 1 (its output is the raw frame)
+  vrt::KArgs a = make_args(ctx, s, cam, p, 0, h, 1);
+  a.alpha = 1.0f;
+  a.prev = ctx->d_rp_raw.p;
+  a.cur = ctx->d_rp_raw.p;
+  launch(ctx, s, a, nullptr, nullptr, nullptr, ms, stats ? ctx->ev_rp_beg : nullptr, nullptr);
+  VRT_HIP(ctx, hipGetLastError());
+  // 2. noise-free geometry buffers: a noised primary ray's hit belongs at another screen position
+  vrt_params geom = *p;
+  geom.ray_noise = 0.0f;
+  if ((st = enqueue_ids(ctx, cam, &geom, 0, h, w, ctx->d_rp_ids[cur].p, ctx->d_rp_depth.p, ms)) != VRT_OK) return st;
+  // 3. the filter against the previous call's frame, IDs and matrix
+  const bool hist = ctx->rp_valid;
+  st = enqueue_reproject(ctx, cam, &geom, ctx->rp_pv, alpha, 0, h, w, ctx->d_rp_raw.p, ctx->d_rp_ids[cur].p, ctx->d_rp_depth.p,
+                         hist ? ctx->d_rp_out[prev].p : nullptr, hist ? ctx->d_rp_ids[prev].p : nullptr, w,
+                         ctx->d_rp_out[cur].p, nullptr, ms, nullptr, stats ? ctx->ev_rp_end : nullptr);
+  if (st != VRT_OK) return st;
+  // 4. to the host through the pinned staging
+  VRT_HIP(ctx, hipMemcpyAsync(ctx->h_stage.p, ctx->d_rp_out[cur].p, bytes, hipMemcpyDeviceToHost, ms));
+  VRT_HIP(ctx, hipStreamSynchronize(ms));
+  std::memcpy(out_rgba8, ctx->h_stage.p, bytes);
+  if (stats) {  // the span from the first launch's start to the last launch's end, as vrt_render_frame's
+    float ms_span = 0.0f;
+    VRT_HIP(ctx, hipEventElapsedTime(&ms_span, ctx->ev_rp_beg, ctx->ev_rp_end));
+    stats->kernel_ms = ms_span;
+  }
+  // this frame is the next call's history, if its camera has a forward matrix
+  ctx->rp_cur = cur;
+  ctx->rp_valid = vrt_camera_forward(cam, ctx->rp_pv) == VRT_OK;
+  ctx->err.clear();
+  return VRT_OK;
+}
+
+int vrt_reprojected_history_reset(vrt_ctx* ctx) {
+  if (!ctx) return VRT_ERR_INVALID;
+  ctx->rp_valid = false;
+  return VRT_OK;
+}
+
+// ---- shaded ray queries (vrt_trace_kernels.h) --------------------------------------------------
+
+// The params of a trace call: max_reflections and max_transparencies in vrt_params' range 0..8 each (so
+// the stack fits kMaxStack), as VRT_ERR_INVALID, then what the render calls check (check_render_args: the
+// atlas rules, which upload a changed atlas as the render calls do). Last of a call's checks: a call that
+// fails another check uploads nothing.
+static int check_trace_params(vrt_ctx* ctx, const vrt_camera* cam, const vrt_params* p) {
+  constexpr int32_t kMaxDepth = (vrt::kMaxStack - 1) / 2;
+  if (p->max_reflections < 0 || p->max_transparencies < 0 || p->max_reflections > kMaxDepth ||
+      p->max_transparencies > kMaxDepth)
+    return fail(ctx, VRT_ERR_INVALID, "max_reflections and max_transparencies must be in [0, 8]");
+  return check_render_args(ctx, cam, p);
+}
+
+// Arguments shared by vrt_trace_rays*. Device buffers (the kernel's 16-byte loads and stores) must be
+// 16-byte aligned; host buffers are only copied.
+static int check_trace_rays(vrt_ctx* ctx, const void* rays, int64_t count, const vrt_params* p, const void* out,
+                            bool device, const vrt_camera* dummy) {
+  if (!p) return fail(ctx, VRT_ERR_INVALID, "null params");
+  if (!ctx->sh[0].d_vox_pad) return fail(ctx, VRT_ERR_NO_VOLUME, "no volume uploaded");
+  if (count < 0 || count > (int64_t(1) << 30)) return fail(ctx, VRT_ERR_INVALID, "ray count must be in [0, 2^30]");
+  if (count > 0 && (!rays || !out)) return fail(ctx, VRT_ERR_INVALID, "null ray or output buffer");
+  if (device && count > 0 && ((reinterpret_cast<uintptr_t>(rays) | reinterpret_cast<uintptr_t>(out)) & 15u) != 0)
+    return fail(ctx, VRT_ERR_INVALID, "device ray and output buffers must be 16-byte aligned");
+  return check_trace_params(ctx, dummy, p);
+}
+
+// The rays form needs no camera: a 1 x 1 image whose matrix no lane reads
+static vrt_camera trace_dummy_camera() {
+  vrt_camera cam{};
+  cam.width = cam.height = 1;
+  return cam;
+}
+
+int vrt_trace_rays_async(vrt_ctx* ctx, const vrt_ray* d_rays, int64_t count, const vrt_params* p,
+                         vrt_ray_color* d_out, void* hip_stream) {
+  if (!ctx) return VRT_ERR_INVALID;
+  const vrt_camera cam = trace_dummy_camera();
+  const int st = check_trace_rays(ctx, d_rays, count, p, d_out, true, &cam);
+  if (st != VRT_OK || count == 0) return st;
+  Shard& s = ctx->sh[0];
+  hipEvent_t eb, ee;
+  launch_timing_events(ctx, eb, ee);
+  vrt::launch_ray_trace(make_args(ctx, s, &cam, p, 0, 1, 1), vrt::kTraceRays, s.d_vox_pad, d_rays, uint32_t(count),
+                        d_out, static_cast<hipStream_t>(hip_stream), eb, ee);
+  VRT_HIP(ctx, hipGetLastError());
+  return VRT_OK;
+}
+
+int vrt_trace_rays(vrt_ctx* ctx, const vrt_ray* rays, int64_t count, const vrt_params* p, vrt_ray_color* out) {
+  if (!ctx) return VRT_ERR_INVALID;
+  const vrt_camera cam = trace_dummy_camera();
+  const int st = check_trace_rays(ctx, rays, count, p, out, false, &cam);
+  if (st != VRT_OK || count == 0) return st;
+  Shard& s = ctx->sh[0];
+  return run_query_staged(ctx, make_args(ctx, s, &cam, p, 0, 1, 1), vrt::kTraceRays, true, rays,
+                          size_t(count) * sizeof(vrt_ray), size_t(count), out);
+}
+
+int vrt_trace_pixels(vrt_ctx* ctx, const vrt_camera* cam, const vrt_params* p, const int32_t* pixels, int32_t count,
+                     vrt_ray_color* out) {
+  if (!ctx) return VRT_ERR_INVALID;
+  if (!cam || !p) return fail(ctx, VRT_ERR_INVALID, "null camera or params");
+  Shard& s = ctx->sh[0];
+  if (!s.d_vox_pad) return fail(ctx, VRT_ERR_NO_VOLUME, "no volume uploaded");
+  if (const int st = check_image(ctx, cam); st != VRT_OK) return st;
+  if (count < 0) return fail(ctx, VRT_ERR_INVALID, "pixel count must be >= 0");
+  if (count > 0 && (!pixels || !out)) return fail(ctx, VRT_ERR_INVALID, "null pixel or output buffer");
+  int st = check_pixel_list(ctx, cam, pixels, count);
+  if (st != VRT_OK) return st;
+  st = check_trace_params(ctx, cam, p);
+  if (st != VRT_OK || count == 0) return st;
+  // the frame's argument block, as the frame launches fill it (launch): primary_ray reads it
+  vrt::KArgs a = make_args(ctx, s, cam, p, 0, cam->height, 1);
+  return run_query_staged(ctx, a, vrt::kTracePixels, true, pixels, size_t(count) * 2 * sizeof(int32_t),
+                          size_t(count), out);
+}
+
+}  // extern "C"
