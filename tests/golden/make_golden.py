@@ -25,6 +25,7 @@ sys.path.insert(1, os.path.dirname(HERE))
 import oracle  # noqa: E402
 import voxelraytracer_amd as vrt  # noqa: E402
 from adversarial_volumes import base_params, camera_poses, scene_volume  # noqa: E402
+from harness import ref_atlas  # noqa: E402
 
 FIXTURES = [
     # name, scene, N, W, H, R, T, extra params
@@ -54,10 +55,6 @@ FIXTURES = [
      dict(camera_poses(16)["c3"], reflection_noise=base_params().reflection_noise, time=base_params().time)),
 ]
 
-
-def ref_atlas():
-    z = np.load(os.path.join(HERE, "atlas", "atlas_ref128.npz"), allow_pickle=False)
-    return z["atlas"]
 
 PARAM_KEYS = ("time", "ray_noise", "reflection_noise", "refraction_noise", "max_ray_length",
               "max_reflections", "max_transparencies", "color_only", "atlas_size",

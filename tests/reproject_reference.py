@@ -9,6 +9,7 @@ import numpy as np
 
 import oracle
 import voxelraytracer_amd as vrt
+from harness import first_records
 from voxelraytracer_amd import abi
 
 N, W, H = 16, 96, 54
@@ -41,24 +42,22 @@ def params(ray_noise=0.0, time=1.0, **kw):
 
 @functools.lru_cache(maxsize=None)
 def oracle_frame(name, cam_name, ray_noise=0.0, time=1.0, w=W, h=H, n=N):
-    """What the oracle says about every pixel's primary ray (oracle.trace_pixel's first record, as
-    tests/test_gpu_render_ids.py::primary_rays reads it): pos and dir as the ray entered RayMarch, and the
+    """What the oracle says about every pixel's primary ray (oracle.trace_pixel's first record,
+    harness.first_records): pos and dir as the ray entered RayMarch, and the
     ID and depth pass restated from its hit: voxel_index (oracle.render's hit record), face = axis (a tie's
     3 clamped to 2) | 4 if the normal -sign(dir[axis]) is negative | voxel byte << 8, depth =
     (rint(point[axis]) - pos[axis]) / dir[axis] in float32, +inf and face 0 for a miss."""
     cam, p, vox = camera(cam_name, w, h), params(ray_noise, time), scene(name, n)
     _, hits, _ = oracle.render(cam, vox, n, p, threads=4)
-    pos, dirs = np.zeros((h, w, 3), np.float32), np.zeros((h, w, 3), np.float32)
+    recs = first_records(cam, vox, n, p)
+    pos, dirs = recs[..., 9:12].astype(np.float32), recs[..., 12:15].astype(np.float32)
     ids = np.zeros((h, w), dtype=abi.PIXEL_ID_DTYPE)
     depth = np.full((h, w), np.inf, np.float32)
     for py in range(h):
         for px in range(w):
-            recs, _ = oracle.trace_pixel(cam, vox, n, p, px, py, cap=4)
-            r = recs[0]
-            assert r[0] == 1 and r[15] == 0 and r[16] == 1
-            pos[py, px], dirs[py, px] = r[9:12], r[12:15]
+            r = recs[py, px]
             found = r[1] != 0
-            assert found == (hits["voxel_index"][py, px] >= 0)
+            assert found == (hits["voxel_index"][py, px] >= 0), ((px, py), float(r[1]), int(hits["voxel_index"][py, px]))
             if found:
                 a = min(int(r[3]), 2)
                 ids[py, px] = (hits["voxel_index"][py, px], a | (4 if r[12 + a] > 0 else 0) | (int(r[2]) << 8))

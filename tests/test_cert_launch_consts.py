@@ -12,42 +12,16 @@ property is asserted pixel by pixel on the kernel's own floats:
    floor(+-P) + 1.
 Cameras that must set every flag, cameras that must clear the flag concerned, and the wave-uniform float
 work of setup_consts against the kernel's expressions."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import voxelraytracer_amd as vrt
+from harness import ALL, K_CELL, K_LEN, K_W, consts, float_bits as bits
 
 F = np.float32
 RNG = np.random.default_rng(20311)
-K_W, K_LEN, K_CELL = 1, 2, 4
-ALL = K_W | K_LEN | K_CELL
 SMALL = ((64, 48), (96, 54))
 LARGE = ((1920, 1080), (32768, 8))
-
-
-def bits(x):
-    return np.ascontiguousarray(x, np.float32).view(np.uint32)
-
-
-def hook():
-    fn = vrt.lib().vrt_debug_cert_launch_consts
-    fn.restype = C.c_int
-    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p]
-    return fn
-
-
-def consts(m, n, w, h, max_len=100.0, m2=None):
-    """The hook's words as a dict; m, m2: 16 float32 (inv_pv, column-major)."""
-    m = np.ascontiguousarray(m, np.float32)
-    m2 = None if m2 is None else np.ascontiguousarray(m2, np.float32)
-    out = np.zeros(20, np.uint32)
-    assert hook()(m.ctypes.data, None if m2 is None else m2.ctypes.data, n, w, h, max_len, out.ctypes.data) == 0
-    f = out.view(np.float32)
-    return dict(setup=int(out[0]), wn=f[1], wf=f[2], rcp_wn=f[3], rcp_wf=f[4], fl1_up=f[5:8].copy(),
-                fl1_dn=f[8:11].copy(), cell=out[11:14].view(np.int32).copy(), fw=f[14], fh=f[15], half_n=f[16],
-                walk_b0=f[17], max_len2=f[18], vdiv_ok=int(out[19]))
 
 
 def matrix(w, h, **kw):

@@ -4,28 +4,17 @@ pixel and counts the rays where a certified outcome (miss / first event byte + f
 bit) disagrees with the exact walk's. Lattice cameras put rays through voxel edges and corners,
 where the exact walk ties. The GPU tests (test_gpu_certified.py) check the kernel itself."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import voxelraytracer_amd as vrt
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from harness import LATTICE, load_certsim
 
 
 @pytest.fixture(scope="module")
 def sim(built):
-    so = os.path.join(ROOT, "build", "certsim_test.so")
-    os.makedirs(os.path.dirname(so), exist_ok=True)
-    subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-fno-fast-math", "-fopenmp", "-shared",
-                           "-fPIC", "-o", so, os.path.join(ROOT, "scripts", "certsim.c"), "-lm"])
-    L = C.CDLL(so)
-    L.cs_build.argtypes = [C.c_void_p, C.c_int, C.c_int]
-    L.cs_run.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_double, C.c_float,
-                         C.c_void_p]
-    return L
+    return load_certsim()
 
 
 def run(L, vox, n, w, h, pos=None, rot=None):
@@ -52,11 +41,6 @@ def check(o):
                                      ("refraction", 128)])
 def test_certified_default_camera(sim, scene, n):
     check(run(sim, vrt.build_scene(scene, n), n, 160, 90))
-
-
-LATTICE = [((0.0, 0.0, 0.0), (-35.26439, 45.0, 0.0)), ((0.5, 0.5, 0.5), (-35.26439, 45.0, 0.0)),
-           ((0.0, 0.0, 0.0), (0.0, 45.0, 0.0)), ((1.0, -2.0, 3.0), (-45.0, 0.0, 0.0)),
-           ((0.25, 0.75, -0.5), (-30.0, 135.0, 0.0))]
 
 
 @pytest.mark.parametrize("li", range(len(LATTICE)))

@@ -1,9 +1,7 @@
 """Golden fixtures (tests/golden/*.npz, made by tests/golden/make_golden.py from the cross-checked
 CPU oracle): the oracle and the scene builders reproduce them exactly on the CPU; the HIP kernel
 reproduces them on the GPU (hit records bit-exact, colour within 1e-4)."""
-import glob
 import hashlib
-import json
 import os
 
 import numpy as np
@@ -11,37 +9,13 @@ import pytest
 
 import oracle
 import voxelraytracer_amd as vrt
-from adversarial_volumes import scene_volume
-from voxelraytracer_amd import abi
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-FILES = sorted(glob.glob(os.path.join(HERE, "golden", "*.npz")))
-
-
-def load(path):
-    z = np.load(path, allow_pickle=False)
-    meta = json.loads(str(z["meta"]))
-    cam = abi.Camera()
-    cam.inv_pv = (abi.C.c_float * 16)(*z["inv_pv"].tolist())
-    cam.width, cam.height = meta["width"], meta["height"]
-    p = vrt.default_params(meta["params"]["max_reflections"], meta["params"]["max_transparencies"])
-    for k, v in meta["params"].items():
-        if k == "sun_dir":
-            p.sun_dir = (abi.C.c_float * 3)(*v)
-        else:
-            setattr(p, k, v)
-    if "atlas" in z.files and z["atlas"].size:
-        p = vrt.textured_params(p, z["atlas"], meta["params"]["atlas_texture_size"])
-    vox = scene_volume(meta["scene"], meta["n"], meta["seed"])
-    return z, meta, cam, p, vox
+from harness import GOLDEN as FILES, load_golden as load, ref_atlas_fixture
 
 
 def test_reference_atlas_fixture():
     """tests/golden/atlas/atlas_ref128.npz holds the reference's decoded textures
     (main.cpp:187-193): 256x256 RGBA8, opaque stone/dirt/grass, glass alpha exactly {0, 255}."""
-    z = np.load(os.path.join(HERE, "golden", "atlas", "atlas_ref128.npz"), allow_pickle=False)
-    a = z["atlas"]
-    meta = json.loads(str(z["meta"]))
+    a, meta = ref_atlas_fixture()
     assert a.shape == (256, 256, 4) and a.dtype == np.uint8
     assert set(meta["png_sha256"]) == {f"{k}128.png" for k in vrt.ATLAS_SLOTS}
     for name, (tx, ty) in vrt.ATLAS_SLOTS.items():

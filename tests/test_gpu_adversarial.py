@@ -24,19 +24,17 @@ import numpy as np
 import pytest
 import torch
 
+import harness
 import oracle
 import voxelraytracer_amd as vrt
 from adversarial_volumes import (CAMERA_IDS, H, NAMES, W, base_params, camera, check_conditions,
                                  sees_a_clamped_byte, volumes)
+from harness import (all_modes, all_pixels, assert_ids_equal_pick, assert_same_packed, check_raw, compare,
+                     depth_restated, reset_modes, synthetic_atlas)
+from harness import float_bits as bits
+from ray_oracle import assert_matches_oracle, assert_nearest_matches, march_all, numpy_shadow, oracle_records, ray_list
+from ray_oracle import make_params as ray_params
 from skipfield_reference import apply_edit, packed_reference
-from test_gpu_cert_lean import reset_modes
-from test_gpu_parity import COLOR_TOL, compare
-from test_gpu_ray_query import assert_nearest_matches, march_all, numpy_shadow
-from test_gpu_ray_trace import assert_matches_oracle, oracle_records, ray_list
-from test_gpu_ray_trace import make_params as ray_params
-from test_gpu_render_ids import all_pixels, assert_ids_equal_pick, depth_restated
-from test_gpu_temporal import check_raw
-from test_gpu_volume_edit import assert_same_packed
 from voxelraytracer_amd import abi
 
 pytestmark = pytest.mark.gpu
@@ -48,18 +46,11 @@ CASES = [(name, n) for name in NAMES for n in SIZES]
 VARIANT_CAMERAS = ("c0", "c3")   # also rendered with ray and refraction noise, and textured
 
 
-@functools.lru_cache(maxsize=None)
-def atlas():
-    a = vrt.make_atlas(32, 16)
-    a.setflags(write=False)
-    return a
-
-
 def make_params(bounces, variant="base"):
     if variant == "noisy":
         return base_params(*bounces, ray_noise=0.02, refraction_noise=0.01)
     p = base_params(*bounces)
-    return vrt.textured_params(p, atlas(), 16) if variant == "textured" else p
+    return vrt.textured_params(p, synthetic_atlas(32, 16), 16) if variant == "textured" else p
 
 
 def variants(cid):
@@ -79,10 +70,6 @@ def oracle_frame(name, n, cid, bounces=(4, 4), variant="base"):
     return rgba, hits, cnt
 
 
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
 def colour_difference(rgba_g, rgba_o, what):
     d = float(np.abs(np.clip(rgba_g[..., :3], 0, 1) - np.clip(rgba_o[..., :3], 0, 1)).max())
     print(f"adversarial colour {what}: max |clamped colour difference| {d:.3e}")
@@ -95,17 +82,6 @@ def float_frame(r, cam, p):
     r.render_rows_async(cam, p, 0, cam.height, 1, out.data_ptr())
     torch.cuda.synchronize()
     return out.cpu().numpy()
-
-
-def all_modes(r):
-    """set_certified x set_cert_trees x set_exact_pass, set on r one after another."""
-    for cert in (-1, 0, 1):
-        for trees in (0, 2):
-            for exact in (0, 2):
-                r.set_certified(cert)
-                r.set_cert_trees(trees)
-                r.set_exact_pass(exact)
-                yield cert, trees, exact
 
 
 # ---- a. the hit-record instance against the C oracle ---------------------------------------------
@@ -132,32 +108,28 @@ def test_hit_records_match_the_oracle(built, name, n):
 def test_stats_free_frames_equal_the_exact_frame(built, name, n):
     vox = volumes(n)[name]
     with vrt.Renderer(0) as r:
-        try:
-            want = {}
-            for layout in (8, 1):
-                reset_modes(r)
-                r.set_skip_layout(layout)
-                r.upload_volume(vox, n)   # a layout takes effect at the next upload
-                assert r._lib.vrt_volume_octants(r._h) == layout
-                for cid in CAMERA_IDS:
-                    cam = camera(n, cid)
-                    for variant in variants(cid):
-                        p = make_params((4, 4), variant)
-                        reset_modes(r)
-                        exact, hits, _ = r.render(cam, p)
-                        if layout == 8:   # (a)'s frame: the exact instance's, whose hit records are the oracle's
-                            _, hits_o, _ = oracle_frame(name, n, cid, (4, 4), variant)
-                            assert np.array_equal(hits["voxel_index"], hits_o["voxel_index"])
-                            assert np.array_equal(bits(hits["ray_length"]), bits(hits_o["ray_length"]))
-                            want[cid, variant] = exact
-                        assert np.array_equal(bits(exact), bits(want[cid, variant])), (layout, cid, variant)
-                        for mode in all_modes(r):
-                            got = float_frame(r, cam, p)
-                            bad = np.argwhere(np.any(bits(got) != bits(want[cid, variant]), axis=-1))
-                            assert bad.size == 0, (layout, cid, variant, mode, len(bad), bad[:5].tolist())
-        finally:
+        want = {}
+        for layout in (8, 1):
             reset_modes(r)
-            r.set_skip_layout(0)
+            r.set_skip_layout(layout)
+            r.upload_volume(vox, n)   # a layout takes effect at the next upload
+            assert r._lib.vrt_volume_octants(r._h) == layout
+            for cid in CAMERA_IDS:
+                cam = camera(n, cid)
+                for variant in variants(cid):
+                    p = make_params((4, 4), variant)
+                    reset_modes(r)
+                    exact, hits, _ = r.render(cam, p)
+                    if layout == 8:   # (a)'s frame: the exact instance's, whose hit records are the oracle's
+                        _, hits_o, _ = oracle_frame(name, n, cid, (4, 4), variant)
+                        assert np.array_equal(hits["voxel_index"], hits_o["voxel_index"])
+                        assert np.array_equal(bits(hits["ray_length"]), bits(hits_o["ray_length"]))
+                        want[cid, variant] = exact
+                    assert np.array_equal(bits(exact), bits(want[cid, variant])), (layout, cid, variant)
+                    for mode in all_modes(r):
+                        got = float_frame(r, cam, p)
+                        bad = np.argwhere(np.any(bits(got) != bits(want[cid, variant]), axis=-1))
+                        assert bad.size == 0, (layout, cid, variant, mode, len(bad), bad[:5].tolist())
 
 
 # ---- c. the automatic mode -----------------------------------------------------------------------
@@ -175,21 +147,18 @@ def test_automatic_mode_follows_the_glass_share(built, name, n):
     assert expect is {"empty": True, "glass_solid": False}.get(name, expect)
     cam, p = camera(n, "c3"), make_params((4, 4))
     with vrt.Renderer(0) as r:
-        try:
-            r.upload_volume(vox, n)
-            assert r.certified() is True          # cert_trees = 1, the default
-            r.set_cert_trees(0)
-            assert r.certified() is expect        # the glass-share rule alone
-            auto = float_frame(r, cam, p)
-            r.set_certified(1)
-            assert r.certified() is True
-            on = float_frame(r, cam, p)
-            r.set_certified(-1)
-            assert r.certified() is False
-            off = float_frame(r, cam, p)
-            exact, _, _ = r.render(cam, p)
-        finally:
-            reset_modes(r)
+        r.upload_volume(vox, n)
+        assert r.certified() is True          # cert_trees = 1, the default
+        r.set_cert_trees(0)
+        assert r.certified() is expect        # the glass-share rule alone
+        auto = float_frame(r, cam, p)
+        r.set_certified(1)
+        assert r.certified() is True
+        on = float_frame(r, cam, p)
+        r.set_certified(-1)
+        assert r.certified() is False
+        off = float_frame(r, cam, p)
+        exact, _, _ = r.render(cam, p)
     assert np.array_equal(bits(auto), bits(exact))
     assert np.array_equal(bits(on), bits(exact))
     assert np.array_equal(bits(off), bits(exact))
@@ -223,17 +192,9 @@ def test_temporal_frame(built, name, n):
 
 @functools.lru_cache(maxsize=None)
 def primary_rays(n, cid):
-    """pos and dir of every pixel's primary ray as it entered RayMarch (tests/test_gpu_render_ids.py): the
-    first record of oracle.trace_pixel. The ray depends on the volume through its size alone, so the empty
-    volume serves, whose trees are one ray."""
-    cam, p, vox = camera(n, cid), make_params((4, 4)), volumes(n)["empty"]
-    pos, dirs = np.zeros((H, W, 3), np.float32), np.zeros((H, W, 3), np.float32)
-    for py in range(H):
-        for px in range(W):
-            recs, _ = oracle.trace_pixel(cam, vox, n, p, px, py, cap=4)
-            assert recs[0, 0] == 1 and recs[0, 15] == 0 and recs[0, 16] == 1
-            pos[py, px], dirs[py, px] = recs[0, 9:12], recs[0, 12:15]
-    return pos, dirs
+    """pos and dir of every pixel's primary ray as it entered RayMarch (harness.primary_rays). The ray depends
+    on the volume through its size alone, so the empty volume serves, whose trees are one ray."""
+    return harness.primary_rays(camera(n, cid), volumes(n)["empty"], n, make_params((4, 4)))
 
 
 @pytest.mark.parametrize("name,n", CASES)
@@ -274,7 +235,7 @@ def rays16():
 @pytest.mark.parametrize("name", NAMES)
 def test_cast_rays_match_the_oracles(built, name):
     """nearest: every field against oracle.march_one; occlusion: the blocked bit, the steps and the flags
-    against numpy_oracle.Tracer.march_shadow (tests/test_gpu_ray_query.py). N = 16."""
+    against numpy_oracle.Tracer.march_shadow (tests/ray_oracle.py). N = 16."""
     vox, rays = volumes(16)[name], rays16()
     near_want = march_all(vox, rays)
     occ_want = [numpy_shadow(vox, ray) for ray in rays]
@@ -302,7 +263,7 @@ def test_cast_rays_match_the_oracles(built, name):
                                            ("lattice", False)])
 def test_trace_rays_match_the_numpy_oracle(built, name, textured):
     """The same rays through the whole ray tree at (4, 4) against numpy_oracle.Tracer
-    (tests/test_gpu_ray_trace.py::oracle_records), once textured. N = 16."""
+    (tests/ray_oracle.py::oracle_records), once textured. N = 16."""
     vox, rays = volumes(16)[name], rays16()
     p = ray_params((4, 4), "noisy", textured)
     want, pops = oracle_records(vox, rays, p)

@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import voxelraytracer_amd as vrt
+from harness import band, batch, current_stream
 from voxelraytracer_amd.tiles import FrameTiler, block_band_spec, row_pitch
 
 pytestmark = pytest.mark.gpu
@@ -25,22 +26,12 @@ def params_for(R, T, nf):
 
 
 def singles(r, cams, ps, row0, rows, step, block):
-    out = []
-    for cam, p in zip(cams, ps):
-        buf = torch.zeros((rows, cam.width), dtype=torch.int32, device="cuda")
-        r.render_temporal_rows_async(cam, p, 1.0, row0, rows, step, buf.data_ptr(), buf.data_ptr(),
-                                     stream=torch.cuda.current_stream().cuda_stream, row_block=block)
-        out.append(buf)
-    torch.cuda.synchronize()
-    return [b.cpu().numpy() for b in out]
+    return [band(r, cam, p, row0, rows, step, block) for cam, p in zip(cams, ps)]
 
 
 def batched(r, cams, ps, row0, rows, step, block):
-    bufs = [torch.full((rows, cams[0].width), 7, dtype=torch.int32, device="cuda") for _ in cams]
-    r.render_temporal_batch_async(cams, ps, row0, rows, step, [b.data_ptr() for b in bufs],
-                                  stream=torch.cuda.current_stream().cuda_stream, row_block=block)
-    torch.cuda.synchronize()
-    return [b.cpu().numpy() for b in bufs]
+    """The buffers start as 7s: equal frames show that the launch wrote every word."""
+    return batch(r, cams, ps, row0, rows, step, block, fill=7)
 
 
 @pytest.mark.parametrize("scene,n,w,h,R,T,nf,ranks,rank", [
@@ -155,8 +146,7 @@ def test_frame_tiler_batches(built, batch, lanes, frames):
         row0, rows, step = block_band_spec(rank, ranks, h, block)
         ref = torch.zeros((rows, w, 4), dtype=torch.uint8, device=dev)
         r.render_temporal_rows_async(cam, p, 1.0, row0, rows, step, ref.data_ptr(), ref.data_ptr(),
-                                     stream=torch.cuda.current_stream().cuda_stream,
-                                     pitch=row_pitch(ref), row_block=block)
+                                     stream=current_stream(), pitch=row_pitch(ref), row_block=block)
         got = []
         for _ in range(frames):
             got.append(tiler.frame())

@@ -9,25 +9,10 @@ import pytest
 import torch
 
 import voxelraytracer_amd as vrt
+from harness import current_stream, frames
 from voxelraytracer_amd.tiles import band_frame_rows, block_band_spec
 
 pytestmark = pytest.mark.gpu
-
-
-def band_frames(r, cam, R, T, alpha, row0, rows, step, block, exact_pass, n_frames=2, counters=False):
-    r.set_exact_pass(exact_pass)
-    w = cam.width
-    hist = torch.zeros((rows, w, 4), dtype=torch.uint8, device="cuda")
-    cnt = torch.zeros(len(vrt.COUNTER_NAMES), dtype=torch.int64, device="cuda")
-    out = []
-    for t in range(n_frames):
-        p = vrt.default_params(R, T, time=float(t + 1))
-        r.render_temporal_rows_async(cam, p, alpha, row0, rows, step, hist.data_ptr(), hist.data_ptr(),
-                                     d_counters=cnt.data_ptr() if counters else 0,
-                                     stream=torch.cuda.current_stream().cuda_stream, row_block=block)
-        torch.cuda.synchronize()
-        out.append(hist.cpu().numpy().copy())
-    return out
 
 
 CASES = [  # scene, n, w, h, R, T, world, block
@@ -45,17 +30,17 @@ def test_block_bands_equal_the_whole_frame(built, case):
     with vrt.Renderer(0) as r:
         r.upload_volume(vox, n)
         cam = vrt.make_camera(w, h)
-        full = band_frames(r, cam, R, T, 0.5, 0, h, 1, 1, 1, counters=True)   # exact STATS instance
+        full = frames(r, cam, 2, R, T, 0.5, 0, h, 1, 1, 1, counters=True)   # exact STATS instance
         for rank in range(world):
             row0, rows, step = block_band_spec(rank, world, h, block)
             if rows == 0:
                 continue
             idx = band_frame_rows(row0, rows, step, block).numpy()
             for mode in (2, 0):   # deferred exact pass, in-lane exact path
-                got = band_frames(r, cam, R, T, 0.5, row0, rows, step, block, mode)
+                got = frames(r, cam, 2, R, T, 0.5, row0, rows, step, mode, block)
                 for k in range(2):
                     assert np.array_equal(got[k], full[k][idx]), (rank, mode, k)
-            ref = band_frames(r, cam, R, T, 0.5, row0, rows, step, block, 1, counters=True)
+            ref = frames(r, cam, 2, R, T, 0.5, row0, rows, step, 1, block, counters=True)
             for k in range(2):
                 assert np.array_equal(ref[k], full[k][idx]), (rank, "stats", k)
 
@@ -68,7 +53,7 @@ def test_block_band_float_output_and_arguments(built):
         r.upload_volume(vrt.build_scene("refraction", n), n)
         cam = vrt.make_camera(w, h)
         p = vrt.default_params(4, 4)
-        st = torch.cuda.current_stream().cuda_stream
+        st = current_stream()
         full = torch.zeros((h, w, 4), dtype=torch.float32, device="cuda")
         r.render_rows_async(cam, p, 0, h, 1, full.data_ptr(), stream=st)
         row0, rows, step = block_band_spec(1, 3, h, 8)
@@ -93,10 +78,10 @@ def test_c4_eight_way_split_at_full_size(built):
     with vrt.Renderer(0) as r:
         r.build_scene_device("terrain", n)
         cam = vrt.make_camera(w, h)
-        full = band_frames(r, cam, R, T, 1.0, 0, h, 1, 1, 1, n_frames=1, counters=True)[0]
+        full = frames(r, cam, 1, R, T, 1.0, 0, h, 1, 1, 1, counters=True)[0]
         for rank in range(world):
             row0, rows, step = block_band_spec(rank, world, h, block)
             idx = band_frame_rows(row0, rows, step, block).numpy()
             for mode in (1, 0):   # automatic deferred exact pass (the timed path), in-lane
-                got = band_frames(r, cam, R, T, 1.0, row0, rows, step, block, mode, n_frames=1)[0]
+                got = frames(r, cam, 1, R, T, 1.0, row0, rows, step, mode, block)[0]
                 assert np.array_equal(got, full[idx]), (rank, mode)

@@ -12,16 +12,13 @@ Frames 64x48 at 16^3 and 96x54 at 32^3: refraction, terrain (with its glass wall
 the adversarial material bytes volume. Certified trees are a colour-only mode, so textured launches run
 with them off only. The CPU test's group of non-finite matrices stays on the host (its flags are asserted
 through the hook there): such a frame's rays are all NaN and say nothing about the set-up."""
-import ctypes as C
-import functools
-import os
-
 import numpy as np
 import pytest
 
 import voxelraytracer_amd as vrt
-from adversarial_volumes import volumes
-from test_cert_launch_consts import ALL, K_CELL, K_LEN, K_W, consts
+from adversarial_volumes import scene_volume
+from harness import (ALL, K_CELL, K_LEN, K_W, assert_equal, band, batch, certified_mode, consts, ref_atlas,
+                     reset_modes)
 
 pytestmark = pytest.mark.gpu
 
@@ -57,62 +54,9 @@ def cameras(n, w, h):
     )
 
 
-@functools.lru_cache(maxsize=None)
-def ref_atlas():
-    path = os.path.join(os.path.dirname(__file__), "golden", "atlas", "atlas_ref128.npz")
-    return np.load(path, allow_pickle=False)["atlas"]
-
-
 def params(textured, **kw):
     p = vrt.default_params(4, 4, **kw)
     return vrt.textured_params(p, ref_atlas(), 128) if textured else p
-
-
-def band(r, cam, p, row0=0, rows=None, counters=False):
-    import torch
-
-    rows = cam.height if rows is None else rows
-    out = torch.zeros((rows, cam.width), dtype=torch.int32, device="cuda")
-    cnt = torch.zeros(len(vrt.COUNTER_NAMES), dtype=torch.int64, device="cuda")
-    r.render_temporal_rows_async(cam, p, 1.0, row0, rows, 1, out.data_ptr(), out.data_ptr(),
-                                 d_counters=cnt.data_ptr() if counters else 0,
-                                 stream=torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
-    return out.cpu().numpy()
-
-
-def batch(r, cams, ps):
-    import torch
-
-    h, w = cams[0].height, cams[0].width
-    out = [torch.zeros((h, w), dtype=torch.int32, device="cuda") for _ in cams]
-    r.render_temporal_batch_async(cams, ps, 0, h, 1, [b.data_ptr() for b in out],
-                                  stream=torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
-    return [b.cpu().numpy() for b in out]
-
-
-def exact_mode(r):
-    r.set_certified(0)
-    r.set_cert_trees(1)
-    r.set_exact_pass(1)
-
-
-def certified_mode(r, trees):
-    r.set_certified(1)
-    r.set_cert_trees(trees)
-    r.set_exact_pass(2)
-
-
-def assert_equal(got, ref, what):
-    bad = np.argwhere(got != ref)
-    assert bad.size == 0, (what, len(bad), bad[:5].tolist())
-
-
-def scene_bytes(scene, n):
-    if scene.startswith("adversarial/"):
-        return volumes(n)[scene.split("/")[1]]
-    return vrt.build_scene(scene, n)
 
 
 def matrix_of(cam):
@@ -131,27 +75,24 @@ def test_timed_path_equals_exact_instance(built, scene, n, w, h, textured):
     assert seen == ALL | (ALL << 4)  # every flag set by some camera and clear for another
     assert consts(matrix_of(cams[0][1]), n, w, h, m2=matrix_of(cams[1][1]))["setup"] == 0
     with vrt.Renderer(0) as r:
-        r.upload_volume(scene_bytes(scene, n), n)
-        try:
-            for i, (cid, cam, _) in enumerate(cams):
-                p = params(textured)
-                p2 = [params(textured, time=1.0), params(textured, time=2.0)]
-                other = cams[(i + 1) % len(cams)][1]
-                exact_mode(r)
-                ref = band(r, cam, p, counters=True)
-                ref2 = [band(r, cam, p2[0], counters=True), band(r, other, p2[1], counters=True),
-                        band(r, cam, p2[1], counters=True)]
-                for t in ((0,) if textured else (0, 2)):
-                    certified_mode(r, t)
-                    what = (scene, n, cid, textured, t)
-                    assert_equal(band(r, cam, p), ref, what + ("frame",))
-                    assert_equal(band(r, cam, p, row0=16, rows=16), ref[16:32], what + ("band",))
-                    if not textured:  # frame batches are colour-only launches
-                        got = batch(r, [cam, other], p2)
-                        assert_equal(got[0], ref2[0], what + ("batch", 0))
-                        assert_equal(got[1], ref2[1], what + ("batch", 1))
-                        got = batch(r, [cam, cam], p2)
-                        assert_equal(got[0], ref2[0], what + ("same-camera batch", 0))
-                        assert_equal(got[1], ref2[2], what + ("same-camera batch", 1))
-        finally:
-            exact_mode(r)
+        r.upload_volume(scene_volume(scene, n), n)
+        for i, (cid, cam, _) in enumerate(cams):
+            p = params(textured)
+            p2 = [params(textured, time=1.0), params(textured, time=2.0)]
+            other = cams[(i + 1) % len(cams)][1]
+            reset_modes(r)
+            ref = band(r, cam, p, counters=True)
+            ref2 = [band(r, cam, p2[0], counters=True), band(r, other, p2[1], counters=True),
+                    band(r, cam, p2[1], counters=True)]
+            for t in ((0,) if textured else (0, 2)):
+                certified_mode(r, t)
+                what = (scene, n, cid, textured, t)
+                assert_equal(band(r, cam, p), ref, what + ("frame",))
+                assert_equal(band(r, cam, p, row0=16, rows=16), ref[16:32], what + ("band",))
+                if not textured:  # frame batches are colour-only launches
+                    got = batch(r, [cam, other], p2)
+                    assert_equal(got[0], ref2[0], what + ("batch", 0))
+                    assert_equal(got[1], ref2[1], what + ("batch", 1))
+                    got = batch(r, [cam, cam], p2)
+                    assert_equal(got[0], ref2[0], what + ("same-camera batch", 0))
+                    assert_equal(got[1], ref2[2], what + ("same-camera batch", 1))

@@ -7,45 +7,16 @@ face and corner of the volume, whose walks land in and cross layers 0 and N - 1;
 fixture's camera against the oracle's frame."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
-import torch
 
 import oracle
 import voxelraytracer_amd as vrt
-from test_golden import FILES as GOLDEN, load as load_golden
+from harness import GOLDEN, band, batch, certified_modes, edge_cameras, load_certsim, load_golden, reset_modes
 from voxelraytracer_amd.tiles import block_band_spec
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def band(r, cam, p, row0, rows, step, block=1, counters=False):
-    """One band at alpha 1 as [rows, W] RGBA8 words; counters: by the exact STATS instance."""
-    out = torch.zeros((rows, cam.width), dtype=torch.int32, device="cuda")
-    cnt = torch.zeros(len(vrt.COUNTER_NAMES), dtype=torch.int64, device="cuda")
-    r.render_temporal_rows_async(cam, p, 1.0, row0, rows, step, out.data_ptr(), out.data_ptr(),
-                                 d_counters=cnt.data_ptr() if counters else 0,
-                                 stream=torch.cuda.current_stream().cuda_stream, row_block=block)
-    torch.cuda.synchronize()
-    return out.cpu().numpy()
-
-
-def certified_modes(r):
-    """The certified pass with the deferred exact pass at any size: plain and with bounce trees."""
-    for trees in (0, 2):
-        r.set_certified(1)
-        r.set_cert_trees(trees)
-        r.set_exact_pass(2)
-        yield trees
-
-
-def reset_modes(r):
-    r.set_certified(0)
-    r.set_cert_trees(1)
-    r.set_exact_pass(1)
 
 
 @pytest.mark.parametrize("path", GOLDEN, ids=[os.path.basename(f)[:-4] for f in GOLDEN])
@@ -61,15 +32,12 @@ def test_certified_pass_reproduces_golden(built, path):
     _, want = oracle.temporal(z["rgba"], np.zeros(z["rgba"].shape, np.uint8), 1.0)
     with vrt.Renderer(0) as r:
         r.upload_volume(vox, meta["n"])
-        try:
-            ref = band(r, cam, p, 0, h, 1, counters=True)
-            for trees in certified_modes(r):
-                got = band(r, cam, p, 0, h, 1)
-                assert np.array_equal(got, ref), trees
-                d = np.abs(got.view(np.uint8).reshape(h, w, 4).astype(np.int16) - want.astype(np.int16))
-                assert d.max() <= 1, (trees, int(d.max()))
-        finally:
-            reset_modes(r)
+        ref = band(r, cam, p, counters=True)
+        for trees in certified_modes(r):
+            got = band(r, cam, p)
+            assert np.array_equal(got, ref), trees
+            d = np.abs(got.view(np.uint8).reshape(h, w, 4).astype(np.int16) - want.astype(np.int16))
+            assert d.max() <= 1, (trees, int(d.max()))
 
 
 SHAPES = [(17, 9), (33, 33), (130, 70)]
@@ -84,24 +52,18 @@ def test_frame_shapes_bands_and_batches(built, scene, n, w, h):
     bands = [(0, h, 1, 1)] + [block_band_spec(k, 2, h, 16) + (16,) for k in range(2)]
     with vrt.Renderer(0) as r:
         r.upload_volume(vrt.build_scene(scene, n), n)
-        try:
-            for row0, rows, step, block in bands:
-                if rows == 0:
-                    continue
-                ref = [band(r, cams[f], ps[f], row0, rows, step, block, counters=True) for f in range(2)]
-                for trees in certified_modes(r):
-                    for f in range(2):
-                        got = band(r, cams[f], ps[f], row0, rows, step, block)
-                        assert np.array_equal(got, ref[f]), (row0, rows, step, block, trees, f)
-                    out = [torch.zeros((rows, w), dtype=torch.int32, device="cuda") for _ in range(2)]
-                    r.render_temporal_batch_async(cams, ps, row0, rows, step, [b.data_ptr() for b in out],
-                                                  stream=torch.cuda.current_stream().cuda_stream, row_block=block)
-                    torch.cuda.synchronize()
-                    for f in range(2):
-                        assert np.array_equal(out[f].cpu().numpy(), ref[f]), ("batch", row0, rows, block, trees, f)
-                reset_modes(r)
-        finally:
+        for row0, rows, step, block in bands:
+            if rows == 0:
+                continue
             reset_modes(r)
+            ref = [band(r, cams[f], ps[f], row0, rows, step, block, counters=True) for f in range(2)]
+            for trees in certified_modes(r):
+                for f in range(2):
+                    got = band(r, cams[f], ps[f], row0, rows, step, block)
+                    assert np.array_equal(got, ref[f]), (row0, rows, step, block, trees, f)
+                out = batch(r, cams, ps, row0, rows, step, block)
+                for f in range(2):
+                    assert np.array_equal(out[f], ref[f]), ("batch", row0, rows, block, trees, f)
 
 
 def vertex_div_ranges_ok(inv_pv):
@@ -166,68 +128,15 @@ def test_vertex_division_flag_both_ways(built, name, kw, flag, outside):
     for scene in ("refraction", "glass_cube"):
         with vrt.Renderer(0) as r:
             r.upload_volume(vrt.build_scene(scene, n), n)
-            try:
-                ref = band(r, cam, p, 0, h, 1, counters=True)
-                for trees in certified_modes(r):
-                    assert np.array_equal(band(r, cam, p, 0, h, 1), ref), (scene, trees)
-            finally:
-                reset_modes(r)
+            ref = band(r, cam, p, counters=True)
+            for trees in certified_modes(r):
+                assert np.array_equal(band(r, cam, p), ref), (scene, trees)
 
 
 @pytest.fixture(scope="module")
 def certsim(built):
     """The CPU model of the certified walks (scripts/certsim.c), for the share of unsure pixels."""
-    so = os.path.join(ROOT, "build", "certsim_lean.so")  # (tests/test_certsim.py builds its own copy)
-    os.makedirs(os.path.dirname(so), exist_ok=True)
-    subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-fno-fast-math", "-fopenmp", "-shared",
-                           "-fPIC", "-o", so, os.path.join(ROOT, "scripts", "certsim.c"), "-lm"])
-    L = C.CDLL(so)
-    L.cs_build.argtypes = [C.c_void_p, C.c_int, C.c_int]
-    L.cs_run.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_double, C.c_float,
-                         C.c_void_p]
-    return L
-
-
-def view_direction(cam):
-    """The centre ray's direction (ndc (0, 0)), from the camera's inverse matrix."""
-    m = np.array(cam.inv_pv[:], np.float64)
-    near = np.array([-m[8 + i] + m[12 + i] for i in range(4)])
-    far = np.array([m[8 + i] + m[12 + i] for i in range(4)])
-    d = far[:3] / far[3] - near[:3] / near[3]
-    return d / np.linalg.norm(d)
-
-
-def edge_cameras(n, w, h):
-    """Within one cell of each face and each corner of the volume (world coordinates: the volume is
-    [-n/2, n/2]^3), on half-integer and integer lattice positions, looking outwards (the view
-    direction within 60 degrees of the outward normal, or of the corner's diagonal) and along the
-    faces (at right angles to the normal): of the six axis views, a face diagonal and a space
-    diagonal, those that do."""
-    e = n / 2.0
-    pos = []
-    for axis in range(3):
-        for sgn in (-1.0, 1.0):
-            for inset in (0.5, 1.0):
-                q = [0.5 if inset == 0.5 else 1.0] * 3
-                q[axis] = sgn * (e - inset)
-                o = [0.0, 0.0, 0.0]
-                o[axis] = sgn
-                pos.append((tuple(q), np.array(o), True))
-    for sx in (-1.0, 1.0):
-        for sy in (-1.0, 1.0):
-            for sz in (-1.0, 1.0):
-                pos.append(((sx * (e - 0.5), sy * (e - 0.5), sz * (e - 0.5)),
-                            np.array([sx, sy, sz]) / np.sqrt(3.0), False))
-    rots = [(0.0, 0.0, 0.0), (0.0, 90.0, 0.0), (0.0, 180.0, 0.0), (0.0, 270.0, 0.0), (-89.99, 0.0, 0.0),
-            (89.99, 0.0, 0.0), (0.0, 45.0, 0.0), (0.0, 225.0, 0.0), (-35.26439, 225.0, 0.0), (35.26439, 45.0, 0.0)]
-    cams = []
-    for p, o, face in pos:
-        for rt in rots:
-            cam = vrt.make_camera(w, h, pos=p, rot=rt)
-            c = float(view_direction(cam) @ o)
-            if c > 0.5 or (face and abs(c) < 0.02):
-                cams.append((p, rt, cam))
-    return cams
+    return load_certsim()
 
 
 @pytest.mark.parametrize("scene", ["terrain", "glass_cube", "refraction"])
@@ -251,26 +160,23 @@ def test_landing_and_crossing_at_the_volume_edge(built, certsim, scene):
     pixels = unsure = glass = 0
     with vrt.Renderer(0) as r:
         r.upload_volume(vox, n)
-        try:
-            for pos, rot, cam in edge_cameras(n, w, h):
-                reset_modes(r)
-                ref = band(r, cam, p, 0, h, 1, counters=True)
-                for trees in certified_modes(r):
-                    got = band(r, cam, p, 0, h, 1)
-                    bad = np.argwhere(got != ref)
-                    assert bad.size == 0, (pos, rot, trees, bad[:5].tolist())
-                reset_modes(r)
-                _, hits, _ = r.render(cam, p)
-                vi = hits["voxel_index"].reshape(-1)
-                glass += int(np.count_nonzero(vox[np.maximum(vi, 0)][vi >= 0] == 2))
-                inv = np.array(cam.inv_pv[:], np.float32)
-                o = np.zeros(32, np.float64)
-                certsim.cs_run(inv.ctypes.data, w, h, sun.ctypes.data, C.c_float(p.max_ray_length), 1.0,
-                               C.c_float(1.0 / 64), o.ctypes.data)
-                pixels += w * h
-                unsure += int(o[19])
-        finally:
+        for pos, rot, cam in edge_cameras(n, w, h):
             reset_modes(r)
+            ref = band(r, cam, p, counters=True)
+            for trees in certified_modes(r):
+                got = band(r, cam, p)
+                bad = np.argwhere(got != ref)
+                assert bad.size == 0, (pos, rot, trees, bad[:5].tolist())
+            reset_modes(r)
+            _, hits, _ = r.render(cam, p)
+            vi = hits["voxel_index"].reshape(-1)
+            glass += int(np.count_nonzero(vox[np.maximum(vi, 0)][vi >= 0] == 2))
+            inv = np.array(cam.inv_pv[:], np.float32)
+            o = np.zeros(32, np.float64)
+            certsim.cs_run(inv.ctypes.data, w, h, sun.ctypes.data, C.c_float(p.max_ray_length), 1.0,
+                           C.c_float(1.0 / 64), o.ctypes.data)
+            pixels += w * h
+            unsure += int(o[19])
     plain, trees = (unsure + glass) / pixels, unsure / pixels
     print(f"{scene}: deferred share (model) plain {plain:.3f}, trees {trees:.3f}, over {pixels} pixels")
     assert (trees if scene == "glass_cube" else plain) < 0.5

@@ -10,17 +10,14 @@ two-frame batch, equal to the exact STATS instance byte for byte.
 Frames of 64x48 and 96x64; the built scenes at N = 16 and 32 and the volumes of
 tests/adversarial_volumes.py. max_ray_length 9 makes walks end by the length test."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import voxelraytracer_amd as vrt
-from adversarial_volumes import camera_poses, volumes
+from adversarial_volumes import camera_poses, scene_volume
+from harness import band, batch, certified_mode, load_certsim, reset_modes
 from voxelraytracer_amd.tiles import block_band_spec
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # name, volume (a built scene or adversarial/<name>), N, camera keywords, frame, max_ray_length (None: default)
 LATTICE_DOWN = dict(pos=(1.0, -2.0, 3.0), rot=(-45.0, 0.0, 0.0))
@@ -36,12 +33,6 @@ INPUTS += [
     ("bytes32_default", "adversarial/bytes", 32, "c0", (64, 48), None),
 ]
 IDS = [i[0] for i in INPUTS]
-
-
-def volume_of(scene, n):
-    if scene.startswith("adversarial/"):
-        return volumes(n)[scene[len("adversarial/"):]]
-    return vrt.build_scene(scene, n)
 
 
 def camera_of(n, cam, w, h):
@@ -62,17 +53,7 @@ X = {name: i for i, name in enumerate(
 
 @pytest.fixture(scope="module")
 def certsim(built):
-    so = os.path.join(ROOT, "build", "certsim_one_exit.so")  # (the other tests build their own copies)
-    os.makedirs(os.path.dirname(so), exist_ok=True)
-    subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-fno-fast-math", "-fopenmp", "-shared",
-                           "-fPIC", "-o", so, os.path.join(ROOT, "scripts", "certsim.c"), "-lm"])
-    L = C.CDLL(so)
-    L.cs_build.argtypes = [C.c_void_p, C.c_int, C.c_int]
-    L.cs_run.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_double, C.c_float,
-                         C.c_void_p]
-    L.cs_exits.argtypes = [C.c_void_p]
-    L.cs_exits.restype = C.c_int
-    return L
+    return load_certsim()
 
 
 def model(L, vox, n, cam, p):
@@ -95,7 +76,7 @@ def test_inputs_reach_every_way_out_of_the_loop(certsim):
     certified outcome of the model disagrees with the exact walk beside it."""
     total = np.zeros((2, len(X)))
     for name, scene, n, cam, (w, h), max_len in INPUTS:
-        o, x = model(certsim, volume_of(scene, n), n, camera_of(n, cam, w, h), params_of(max_len))
+        o, x = model(certsim, scene_volume(scene, n), n, camera_of(n, cam, w, h), params_of(max_len))
         assert o[6] == 0 and o[18] == 0, (name, o[6], o[18])
         total += x
     both = total.sum(axis=0)
@@ -110,32 +91,11 @@ def test_inputs_reach_every_way_out_of_the_loop(certsim):
     assert both[X["cap"]] == 0 and both[X["none"]] == 0
 
 
-def band(r, cam, p, row0, rows, step, block=1, counters=False):
-    """One band at alpha 1 as [rows, W] RGBA8 words; counters: by the exact STATS instance."""
-    import torch
-
-    out = torch.zeros((rows, cam.width), dtype=torch.int32, device="cuda")
-    cnt = torch.zeros(len(vrt.COUNTER_NAMES), dtype=torch.int64, device="cuda")
-    r.render_temporal_rows_async(cam, p, 1.0, row0, rows, step, out.data_ptr(), out.data_ptr(),
-                                 d_counters=cnt.data_ptr() if counters else 0,
-                                 stream=torch.cuda.current_stream().cuda_stream, row_block=block)
-    torch.cuda.synchronize()
-    return out.cpu().numpy()
-
-
-def reset_modes(r):
-    r.set_certified(0)
-    r.set_cert_trees(1)
-    r.set_exact_pass(1)
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("name,scene,n,cam,shape,max_len", INPUTS, ids=IDS)
 def test_every_certified_path_equals_the_exact_instance(built, certsim, name, scene, n, cam, shape, max_len):
-    import torch
-
     w, h = shape
-    vox = volume_of(scene, n)
+    vox = scene_volume(scene, n)
     cams = [camera_of(n, cam, w, h), camera_of(n, cam, w, h)]
     ps = [params_of(max_len, time=1.0), params_of(max_len, time=2.0)]
     bands = [(0, h, 1, 1)] + [block_band_spec(k, 2, h, 16) + (16,) for k in range(2)]
@@ -145,34 +105,24 @@ def test_every_certified_path_equals_the_exact_instance(built, certsim, name, sc
     o, _ = model(certsim, vox, n, cams[0], ps[0])
     with vrt.Renderer(0) as r:
         r.upload_volume(vox, n)
-        try:
-            _, hits, _ = r.render(cams[0], ps[0])
-            vi = hits["voxel_index"].reshape(-1)
-            glass = int(np.count_nonzero(np.asarray(vox)[np.maximum(vi, 0)][vi >= 0] == 2))
-            plain, trees = (o[19] + glass) / (w * h), o[19] / (w * h)
-            print(f"{name}: deferred share (model) plain {plain:.3f}, trees {trees:.3f}")
-            assert (trees if scene == "glass_cube" else plain) < 0.5
-            for row0, rows, step, block in bands:
-                if rows == 0:
-                    continue
-                reset_modes(r)
-                ref = [band(r, cams[f], ps[f], row0, rows, step, block, counters=True) for f in range(2)]
-                for trees_mode in (0, 2):
-                    for exact_pass in (0, 2):
-                        r.set_certified(1)
-                        r.set_cert_trees(trees_mode)
-                        r.set_exact_pass(exact_pass)
-                        for f in range(2):
-                            got = band(r, cams[f], ps[f], row0, rows, step, block)
-                            bad = np.argwhere(got != ref[f])
-                            assert bad.size == 0, (row0, rows, block, trees_mode, exact_pass, f, bad[:5].tolist())
-                        out = [torch.zeros((rows, w), dtype=torch.int32, device="cuda") for _ in range(2)]
-                        r.render_temporal_batch_async(cams, ps, row0, rows, step, [b.data_ptr() for b in out],
-                                                      stream=torch.cuda.current_stream().cuda_stream,
-                                                      row_block=block)
-                        torch.cuda.synchronize()
-                        for f in range(2):
-                            assert np.array_equal(out[f].cpu().numpy(), ref[f]), ("batch", row0, rows, block,
-                                                                                   trees_mode, exact_pass, f)
-        finally:
+        _, hits, _ = r.render(cams[0], ps[0])
+        vi = hits["voxel_index"].reshape(-1)
+        glass = int(np.count_nonzero(np.asarray(vox)[np.maximum(vi, 0)][vi >= 0] == 2))
+        plain, trees = (o[19] + glass) / (w * h), o[19] / (w * h)
+        print(f"{name}: deferred share (model) plain {plain:.3f}, trees {trees:.3f}")
+        assert (trees if scene == "glass_cube" else plain) < 0.5
+        for row0, rows, step, block in bands:
+            if rows == 0:
+                continue
             reset_modes(r)
+            ref = [band(r, cams[f], ps[f], row0, rows, step, block, counters=True) for f in range(2)]
+            for trees_mode in (0, 2):
+                for exact_pass in (0, 2):
+                    certified_mode(r, trees_mode, exact_pass)
+                    for f in range(2):
+                        got = band(r, cams[f], ps[f], row0, rows, step, block)
+                        bad = np.argwhere(got != ref[f])
+                        assert bad.size == 0, (row0, rows, block, trees_mode, exact_pass, f, bad[:5].tolist())
+                    out = batch(r, cams, ps, row0, rows, step, block)
+                    for f in range(2):
+                        assert np.array_equal(out[f], ref[f]), ("batch", row0, rows, block, trees_mode, exact_pass, f)

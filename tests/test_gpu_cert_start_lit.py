@@ -11,16 +11,14 @@ volumes 16^3 and 32^3: the six-face shell and the glass clutter of tests/adversa
 
 test_start_cases[glass_clutter-32], camera outside_py at 33x33, is the case that found cert_continuation's
 missing on-plane check: pixel (16, 18) differed in every certified mode until then."""
-import functools
 import os
 
-import numpy as np
 import pytest
 
 import oracle
 import voxelraytracer_amd as vrt
 from adversarial_volumes import volumes
-from test_gpu_temporal import check_raw
+from harness import assert_equal, band, batch, certified_mode, check_raw, ref_atlas, reset_modes, words_to_bytes
 
 pytestmark = pytest.mark.gpu
 
@@ -58,62 +56,11 @@ SUNS.update({"zero_x": (0.0, 0.8, 0.6), "negzero_z": (0.6, 0.8, -0.0), "zero_xz"
 SHAPES = ((64, 48), (33, 33))
 
 
-@functools.lru_cache(maxsize=None)
-def ref_atlas():
-    path = os.path.join(os.path.dirname(__file__), "golden", "atlas", "atlas_ref128.npz")
-    return np.load(path, allow_pickle=False)["atlas"]
-
-
 def params(sun=None, textured=False, **kw):
     if sun is not None:
         kw["sun_dir"] = sun
     p = vrt.default_params(4, 4, **kw)
     return vrt.textured_params(p, ref_atlas(), 128) if textured else p
-
-
-def band(r, cam, p, counters=False):
-    """The whole frame at alpha 1 as [H, W] RGBA8 words; counters: by the exact STATS instance."""
-    import torch
-
-    out = torch.zeros((cam.height, cam.width), dtype=torch.int32, device="cuda")
-    cnt = torch.zeros(len(vrt.COUNTER_NAMES), dtype=torch.int64, device="cuda")
-    r.render_temporal_rows_async(cam, p, 1.0, 0, cam.height, 1, out.data_ptr(), out.data_ptr(),
-                                 d_counters=cnt.data_ptr() if counters else 0,
-                                 stream=torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
-    return out.cpu().numpy()
-
-
-def batch(r, cams, ps):
-    import torch
-
-    h, w = cams[0].height, cams[0].width
-    out = [torch.zeros((h, w), dtype=torch.int32, device="cuda") for _ in cams]
-    r.render_temporal_batch_async(cams, ps, 0, h, 1, [b.data_ptr() for b in out],
-                                  stream=torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
-    return [b.cpu().numpy() for b in out]
-
-
-def exact_mode(r):
-    r.set_certified(0)
-    r.set_cert_trees(1)
-    r.set_exact_pass(1)
-
-
-def certified_mode(r, trees):
-    r.set_certified(1)
-    r.set_cert_trees(trees)
-    r.set_exact_pass(2)
-
-
-def assert_equal(got, ref, what):
-    bad = np.argwhere(got != ref)
-    assert bad.size == 0, (what, len(bad), bad[:5].tolist())
-
-
-def words_to_bytes(a):
-    return np.ascontiguousarray(a).view(np.uint8).reshape(a.shape[0], a.shape[1], 4)
 
 
 def run_cases(name, n, cases, trees=(0,), textured=False, with_oracle=False):
@@ -124,28 +71,25 @@ def run_cases(name, n, cases, trees=(0,), textured=False, with_oracle=False):
     near = 0
     with vrt.Renderer(0) as r:
         r.upload_volume(vox, n)
-        try:
-            for w, h in SHAPES:
-                cams = [vrt.make_camera(w, h, **kw) for _, kw, _ in cases]
-                for i, (cid, _, sun) in enumerate(cases):
-                    p = params(sun, textured)
-                    exact_mode(r)
-                    ref = band(r, cams[i], p, counters=True)
-                    j = (i + 1) % len(cases)
-                    p2 = [params(sun, textured, time=1.0), params(sun, textured, time=2.0)]
-                    ref2 = [band(r, cams[i], p2[0], counters=True), band(r, cams[j], p2[1], counters=True)]
-                    for t in trees:
-                        certified_mode(r, t)
-                        assert_equal(band(r, cams[i], p), ref, (name, n, cid, (w, h), "plain", t))
-                        if not textured:  # frame batches are colour-only launches
-                            got2 = batch(r, [cams[i], cams[j]], p2)
-                            for f in range(2):
-                                assert_equal(got2[f], ref2[f], (name, n, cid, (w, h), "batch", t, f))
-                    if with_oracle and n == 16 and (w, h) == SHAPES[0]:
-                        rgba_o, _, _ = oracle.render(cams[i], vox, n, p, threads=THREADS)
-                        near += check_raw(words_to_bytes(ref), rgba_o)
-        finally:
-            exact_mode(r)
+        for w, h in SHAPES:
+            cams = [vrt.make_camera(w, h, **kw) for _, kw, _ in cases]
+            for i, (cid, _, sun) in enumerate(cases):
+                p = params(sun, textured)
+                reset_modes(r)
+                ref = band(r, cams[i], p, counters=True)
+                j = (i + 1) % len(cases)
+                p2 = [params(sun, textured, time=1.0), params(sun, textured, time=2.0)]
+                ref2 = [band(r, cams[i], p2[0], counters=True), band(r, cams[j], p2[1], counters=True)]
+                for t in trees:
+                    certified_mode(r, t)
+                    assert_equal(band(r, cams[i], p), ref, (name, n, cid, (w, h), "plain", t))
+                    if not textured:  # frame batches are colour-only launches
+                        got2 = batch(r, [cams[i], cams[j]], p2)
+                        for f in range(2):
+                            assert_equal(got2[f], ref2[f], (name, n, cid, (w, h), "batch", t, f))
+                if with_oracle and n == 16 and (w, h) == SHAPES[0]:
+                    rgba_o, _, _ = oracle.render(cams[i], vox, n, p, threads=THREADS)
+                    near += check_raw(words_to_bytes(ref), rgba_o)
     return near
 
 

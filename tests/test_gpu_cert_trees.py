@@ -11,23 +11,10 @@ import pytest
 import torch
 
 import voxelraytracer_amd as vrt
+from harness import band, batch, current_stream, frames
 from voxelraytracer_amd.tiles import block_band_spec
 
 pytestmark = pytest.mark.gpu
-
-
-def frames(r, cam, n_frames, R, T, alpha, row0, rows, step, w, counters=False, **kw):
-    hist = torch.zeros((rows, w, 4), dtype=torch.uint8, device="cuda")
-    cnt = torch.zeros(len(vrt.COUNTER_NAMES), dtype=torch.int64, device="cuda")
-    out = []
-    for t in range(n_frames):
-        p = vrt.default_params(R, T, time=float(t + 1), **kw)
-        r.render_temporal_rows_async(cam, p, alpha, row0, rows, step, hist.data_ptr(), hist.data_ptr(),
-                                     d_counters=cnt.data_ptr() if counters else 0,
-                                     stream=torch.cuda.current_stream().cuda_stream)
-        torch.cuda.synchronize()
-        out.append(hist.cpu().numpy().copy())
-    return out
 
 
 def glass_volume(n, seed):
@@ -62,10 +49,10 @@ def test_cert_trees_are_bit_identical(built, case):
         r.set_cert_trees(2)
         r.set_exact_pass(2)   # deferred at any size
         cam = vrt.make_camera(w, h)
-        a = frames(r, cam, 2, R, T, 0.5, row0, rows, step, w, **kw)
+        a = frames(r, cam, 2, R, T, 0.5, row0, rows, step, **kw)
         r.set_exact_pass(0)
-        b = frames(r, cam, 2, R, T, 0.5, row0, rows, step, w, **kw)
-        ref = frames(r, cam, 2, R, T, 0.5, row0, rows, step, w, counters=True, **kw)
+        b = frames(r, cam, 2, R, T, 0.5, row0, rows, step, **kw)
+        ref = frames(r, cam, 2, R, T, 0.5, row0, rows, step, counters=True, **kw)
     for k in range(2):
         assert np.array_equal(a[k], ref[k]), f"deferred, frame {k}: {int(np.any(a[k] != ref[k], -1).sum())} px"
         assert np.array_equal(b[k], ref[k]), f"in lane, frame {k}"
@@ -90,8 +77,8 @@ def test_cert_trees_lattice_cameras(built, trees):
                              ((-2.5, 0.5, 1.5), (-35.26439, 45.0, 0.0)), ((0.5, 0.5, -40.0), (0.0, 0.0, 0.0)),
                              ((3.0, -1.0, -7.0), (0.0, 90.0, 0.0)), ((0.0, 0.0, -20.0), (-45.0, 0.0, 0.0))]:
                 cam = vrt.make_camera(w, h, pos=pos, rot=rot)
-                a = frames(r, cam, 1, 4, 4, 1.0, 0, h, 1, w)
-                ref = frames(r, cam, 1, 4, 4, 1.0, 0, h, 1, w, counters=True)
+                a = frames(r, cam, 1, 4, 4, 1.0, 0, h, 1)
+                ref = frames(r, cam, 1, 4, 4, 1.0, 0, h, 1, counters=True)
                 bad = np.argwhere(np.any(a[0] != ref[0], axis=-1))
                 assert bad.size == 0, (pos, rot, ep, bad[:5].tolist())
 
@@ -107,20 +94,17 @@ def test_cert_trees_toggled_between_frames(built):
         hist = torch.zeros((h, w, 4), dtype=torch.uint8, device="cuda")
         ref = torch.zeros_like(hist)
         cnt = torch.zeros(len(vrt.COUNTER_NAMES), dtype=torch.int64, device="cuda")
-        s = torch.cuda.current_stream().cuda_stream
-        try:
-            for t, (trees, ep) in enumerate([(2, 2), (1, 2), (2, 2), (0, 2), (2, 2), (2, 0), (2, 2),
-                                             (2, 2), (0, 0), (2, 2)]):
-                p = vrt.default_params(4, 4, time=float(t + 1))
-                r.set_cert_trees(trees)
-                r.set_exact_pass(ep)
-                r.render_temporal_rows_async(cam, p, 0.5, 0, h, 1, hist.data_ptr(), hist.data_ptr(), stream=s)
-                r.render_temporal_rows_async(cam, p, 0.5, 0, h, 1, ref.data_ptr(), ref.data_ptr(),
-                                             d_counters=cnt.data_ptr(), stream=s)
-                torch.cuda.synchronize()
-                assert torch.equal(hist, ref), f"frame {t}"
-        finally:
-            r.set_cert_trees(1)
+        s = current_stream()
+        for t, (trees, ep) in enumerate([(2, 2), (1, 2), (2, 2), (0, 2), (2, 2), (2, 0), (2, 2),
+                                         (2, 2), (0, 0), (2, 2)]):
+            p = vrt.default_params(4, 4, time=float(t + 1))
+            r.set_cert_trees(trees)
+            r.set_exact_pass(ep)
+            r.render_temporal_rows_async(cam, p, 0.5, 0, h, 1, hist.data_ptr(), hist.data_ptr(), stream=s)
+            r.render_temporal_rows_async(cam, p, 0.5, 0, h, 1, ref.data_ptr(), ref.data_ptr(),
+                                         d_counters=cnt.data_ptr(), stream=s)
+            torch.cuda.synchronize()
+            assert torch.equal(hist, ref), f"frame {t}"
 
 
 @pytest.mark.parametrize("ranks,rank,nf", [(1, 0, 3), (8, 3, 8)])
@@ -138,19 +122,10 @@ def test_cert_trees_frame_batches(built, ranks, rank, nf):
         r.set_certified(1)
         r.set_cert_trees(2)
         r.set_exact_pass(2)
-        s = torch.cuda.current_stream().cuda_stream
-        ref = []
-        for f in range(nf):
-            b = torch.zeros((rows, w), dtype=torch.int32, device="cuda")
-            r.render_temporal_rows_async(cams[f], ps[f], 1.0, row0, rows, step, b.data_ptr(), b.data_ptr(),
-                                         stream=s, row_block=block)
-            ref.append(b)
-        got = [torch.zeros((rows, w), dtype=torch.int32, device="cuda") for _ in range(nf)]
-        r.render_temporal_batch_async(cams, ps, row0, rows, step, [b.data_ptr() for b in got], stream=s,
-                                      row_block=block)
-        torch.cuda.synchronize()
+        ref = [band(r, cams[f], ps[f], row0, rows, step, block) for f in range(nf)]
+        got = batch(r, cams, ps, row0, rows, step, block)
     for f in range(nf):
-        assert torch.equal(got[f], ref[f]), f"frame {f}"
+        assert np.array_equal(got[f], ref[f]), f"frame {f}"
 
 
 @pytest.mark.parametrize("scene,n,pos,rot,R,T", [
@@ -169,19 +144,14 @@ def test_certified_start_slivers(built, scene, n, pos, rot, R, T):
     with vrt.Renderer(0) as r:
         r.upload_volume(vrt.build_scene(scene, n), n)
         cam = vrt.make_camera(w, h, pos=pos, rot=rot)
-        ref = frames(r, cam, 1, R, T, 1.0, 0, h, 1, w, counters=True)
-        try:
-            for cert, trees, ep in ((1, 2, 2), (1, 2, 0), (1, 0, 2), (1, 0, 0), (0, 0, 0)):
-                r.set_certified(cert)
-                r.set_cert_trees(trees)
-                r.set_exact_pass(ep)
-                a = frames(r, cam, 1, R, T, 1.0, 0, h, 1, w)
-                bad = np.argwhere(np.any(a[0] != ref[0], axis=-1))
-                assert bad.size == 0, (cert, trees, ep, bad[:5].tolist())
-        finally:
-            r.set_certified(0)
-            r.set_cert_trees(1)
-            r.set_exact_pass(1)
+        ref = frames(r, cam, 1, R, T, 1.0, 0, h, 1, counters=True)
+        for cert, trees, ep in ((1, 2, 2), (1, 2, 0), (1, 0, 2), (1, 0, 0), (0, 0, 0)):
+            r.set_certified(cert)
+            r.set_cert_trees(trees)
+            r.set_exact_pass(ep)
+            a = frames(r, cam, 1, R, T, 1.0, 0, h, 1)
+            bad = np.argwhere(np.any(a[0] != ref[0], axis=-1))
+            assert bad.size == 0, (cert, trees, ep, bad[:5].tolist())
 
 
 @pytest.mark.parametrize("scene,n", [("glass_cube", 64), ("refraction", 64), ("terrain", 64)])
@@ -196,24 +166,20 @@ def test_lattice_camera_sample(built, scene, n):
     with vrt.Renderer(0) as r:
         r.upload_volume(vrt.build_scene(scene, n), n)
         r.set_certified(1)
-        try:
-            for k in range(40):
-                pos = tuple(float(x) for x in np.round(rng.uniform(-n / 2.5, n / 2.5, 3) * 2) / 2)
-                if k % 3 == 0:
-                    pos = tuple(float(round(x)) for x in pos)
-                rot = (float(rng.choice(pitches)), float(rng.choice(yaws)), 0.0)
-                R, T = [(4, 4), (1, 2), (2, 6)][k % 3]
-                cam = vrt.make_camera(w, h, pos=pos, rot=rot)
-                ref = frames(r, cam, 1, R, T, 1.0, 0, h, 1, w, counters=True)
-                for trees, ep in ((2, 2), (2, 0), (0, 2), (0, 0)):
-                    r.set_cert_trees(trees)
-                    r.set_exact_pass(ep)
-                    a = frames(r, cam, 1, R, T, 1.0, 0, h, 1, w)
-                    bad = np.argwhere(np.any(a[0] != ref[0], axis=-1))
-                    assert bad.size == 0, (pos, rot, (R, T), trees, ep, bad[:3].tolist())
-        finally:
-            r.set_cert_trees(1)
-            r.set_exact_pass(1)
+        for k in range(40):
+            pos = tuple(float(x) for x in np.round(rng.uniform(-n / 2.5, n / 2.5, 3) * 2) / 2)
+            if k % 3 == 0:
+                pos = tuple(float(round(x)) for x in pos)
+            rot = (float(rng.choice(pitches)), float(rng.choice(yaws)), 0.0)
+            R, T = [(4, 4), (1, 2), (2, 6)][k % 3]
+            cam = vrt.make_camera(w, h, pos=pos, rot=rot)
+            ref = frames(r, cam, 1, R, T, 1.0, 0, h, 1, counters=True)
+            for trees, ep in ((2, 2), (2, 0), (0, 2), (0, 0)):
+                r.set_cert_trees(trees)
+                r.set_exact_pass(ep)
+                a = frames(r, cam, 1, R, T, 1.0, 0, h, 1)
+                bad = np.argwhere(np.any(a[0] != ref[0], axis=-1))
+                assert bad.size == 0, (pos, rot, (R, T), trees, ep, bad[:3].tolist())
 
 
 @pytest.mark.xfail(strict=True, reason="known, unfixed (DESIGN.md §10, HISTORY r06_s38-s39): the certified "
@@ -230,8 +196,8 @@ def test_certified_shadow_open_cases(built, scene, n, pos, rot, R, T):
     with vrt.Renderer(0) as r:
         r.upload_volume(vrt.build_scene(scene, n), n)
         cam = vrt.make_camera(w, h, pos=pos, rot=rot)
-        ref = frames(r, cam, 1, R, T, 1.0, 0, h, 1, w, counters=True)
+        ref = frames(r, cam, 1, R, T, 1.0, 0, h, 1, counters=True)
         r.set_certified(1)
-        a = frames(r, cam, 1, R, T, 1.0, 0, h, 1, w)
+        a = frames(r, cam, 1, R, T, 1.0, 0, h, 1)
         r.set_certified(0)
         assert np.array_equal(a[0], ref[0])

@@ -3,7 +3,7 @@ cert_walk; tests/test_cert_bound_forms.py holds the CPU restatement) through the
 the deferred exact pass forced, plain and with bounce trees, against the exact STATS instance, bit
 for bit: the default camera; cameras in the cell layer next to each face of the volume, whose
 walks start without a jump box (G <= 1: the flat test's no-jump case from the first iteration);
-and lattice cameras with a direction component near zero (test_certsim.py's list, straight down and
+and lattice cameras with a direction component near zero (harness.LATTICE, straight down and
 the axis views), where |1/d_b| B(u) dominates gam_b. glass_cube's trees walk from uncertain origins
 (e0, ed, len0b != 0); the primary and exact-origin walks run the instance that adds no ed."""
 import pytest
@@ -11,8 +11,7 @@ import pytest
 import numpy as np
 
 import voxelraytracer_amd as vrt
-from test_certsim import LATTICE
-from test_gpu_cert_lean import band, certified_modes, reset_modes
+from harness import LATTICE, band, certified_modes, reset_modes
 
 pytestmark = pytest.mark.gpu
 
@@ -48,7 +47,6 @@ def scene(built, request):
     r = vrt.Renderer(0)
     r.upload_volume(vrt.build_scene(name, n), n)
     yield r, n
-    reset_modes(r)
     r.close()
 
 
@@ -60,9 +58,9 @@ def test_certified_pass_equals_exact_instance(scene, w, h):
         for name, kw in cameras(n):
             cam = vrt.make_camera(w, h, **kw)
             reset_modes(r)
-            ref = band(r, cam, p, 0, h, 1, counters=True)
+            ref = band(r, cam, p, counters=True)
             for trees in certified_modes(r):
-                got = band(r, cam, p, 0, h, 1)
+                got = band(r, cam, p)
                 bad = np.argwhere(got != ref)
                 assert bad.size == 0, (name, trees, len(bad), bad[:5].tolist())
     finally:

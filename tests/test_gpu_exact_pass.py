@@ -14,23 +14,9 @@ import pytest
 import torch
 
 import voxelraytracer_amd as vrt
+from harness import current_stream, frames, ref_atlas
 
 pytestmark = pytest.mark.gpu
-
-
-def frames(r, cam, n_frames, R, T, alpha, row0, rows, step, w, exact_pass, counters=False, **kw):
-    r.set_exact_pass(exact_pass)
-    hist = torch.zeros((rows, w, 4), dtype=torch.uint8, device="cuda")
-    cnt = torch.zeros(len(vrt.COUNTER_NAMES), dtype=torch.int64, device="cuda")
-    out = []
-    for t in range(n_frames):
-        p = vrt.default_params(R, T, time=float(t + 1), **kw)
-        r.render_temporal_rows_async(cam, p, alpha, row0, rows, step, hist.data_ptr(), hist.data_ptr(),
-                                     d_counters=cnt.data_ptr() if counters else 0,
-                                     stream=torch.cuda.current_stream().cuda_stream)
-        torch.cuda.synchronize()
-        out.append(hist.cpu().numpy().copy())
-    return out
 
 
 def random_volume(n, seed, density=0.02):
@@ -58,9 +44,9 @@ def test_exact_pass_is_bit_identical(built, case):
         r.upload_volume(vox, n)
         r.set_certified(1)   # certified pixels also on glass-heavy volumes: many deferred pixels
         cam = vrt.make_camera(w, h)
-        a = frames(r, cam, 3, R, T, 0.5, row0, rows, step, w, 2, **kw)   # deferred, any size
-        b = frames(r, cam, 3, R, T, 0.5, row0, rows, step, w, 0, **kw)
-        ref = frames(r, cam, 3, R, T, 0.5, row0, rows, step, w, 2, counters=True, **kw)
+        a = frames(r, cam, 3, R, T, 0.5, row0, rows, step, 2, **kw)   # deferred, any size
+        b = frames(r, cam, 3, R, T, 0.5, row0, rows, step, 0, **kw)
+        ref = frames(r, cam, 3, R, T, 0.5, row0, rows, step, 2, counters=True, **kw)
     for k in range(3):
         assert np.array_equal(a[k], ref[k]), f"exact pass, frame {k}"
         assert np.array_equal(b[k], ref[k]), f"in-lane, frame {k}"
@@ -75,8 +61,8 @@ def test_exact_pass_lattice_cameras(built):
         for pos, rot in [((0.0, 0.0, 0.0), (-45.0, -45.0, 0.0)), ((1.0, 2.0, -3.0), (0.0, 0.0, 0.0)),
                          ((-2.5, 0.5, 1.5), (-35.26439, 45.0, 0.0))]:
             cam = vrt.make_camera(w, h, pos=pos, rot=rot)
-            a = frames(r, cam, 1, 4, 4, 1.0, 0, h, 1, w, 2)
-            ref = frames(r, cam, 1, 4, 4, 1.0, 0, h, 1, w, 2, counters=True)
+            a = frames(r, cam, 1, 4, 4, 1.0, 0, h, 1, 2)
+            ref = frames(r, cam, 1, 4, 4, 1.0, 0, h, 1, 2, counters=True)
             assert np.array_equal(a[0], ref[0]), pos
 
 
@@ -90,7 +76,7 @@ def test_exact_pass_toggled_between_frames(built):
         hist = torch.zeros((h, w, 4), dtype=torch.uint8, device="cuda")
         ref = torch.zeros_like(hist)
         cnt = torch.zeros(len(vrt.COUNTER_NAMES), dtype=torch.int64, device="cuda")
-        s = torch.cuda.current_stream().cuda_stream
+        s = current_stream()
         for t, on in enumerate([2, 0, 2, 2, 0, 0, 2, 1, 2]):
             p = vrt.default_params(4, 4, time=float(t + 1), ray_noise=0.01 * (t % 2))
             r.set_exact_pass(on)
@@ -99,13 +85,6 @@ def test_exact_pass_toggled_between_frames(built):
                                          d_counters=cnt.data_ptr(), stream=s)
             torch.cuda.synchronize()
             assert torch.equal(hist, ref), f"frame {t} (exact pass {on})"
-
-
-def ref_atlas():
-    """The reference's own textures (res/textures/*128.png) in the ABI atlas layout."""
-    import os
-    path = os.path.join(os.path.dirname(__file__), "golden", "atlas", "atlas_ref128.npz")
-    return np.load(path, allow_pickle=False)["atlas"]
 
 
 TEX_CASES = [
@@ -130,18 +109,7 @@ def test_textured_certified_pixels_bit_identical(built, case):
         cam = vrt.make_camera(w, h)
         out = {}
         for mode, ep, counters in (("defer", 2, False), ("inlane", 0, False), ("exact", 2, True)):
-            r.set_exact_pass(ep)
-            hist = torch.zeros((h, w, 4), dtype=torch.uint8, device="cuda")
-            cnt = torch.zeros(len(vrt.COUNTER_NAMES), dtype=torch.int64, device="cuda")
-            seq = []
-            for t in range(3):
-                p = vrt.textured_params(vrt.default_params(R, T, time=float(t + 1)), atlas)
-                r.render_temporal_rows_async(cam, p, 0.5, 0, h, 1, hist.data_ptr(), hist.data_ptr(),
-                                             d_counters=cnt.data_ptr() if counters else 0,
-                                             stream=torch.cuda.current_stream().cuda_stream)
-                torch.cuda.synchronize()
-                seq.append(hist.cpu().numpy().copy())
-            out[mode] = seq
+            out[mode] = frames(r, cam, 3, R, T, 0.5, 0, h, 1, ep, counters=counters, atlas=atlas)
     for t in range(3):
         assert np.array_equal(out["defer"][t], out["exact"][t]), f"deferred, frame {t}"
         assert np.array_equal(out["inlane"][t], out["exact"][t]), f"in-lane, frame {t}"

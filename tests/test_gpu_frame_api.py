@@ -24,6 +24,7 @@ import pytest
 import torch
 
 import voxelraytracer_amd as vrt
+from harness import hipcopy
 
 pytestmark = pytest.mark.gpu
 
@@ -152,7 +153,7 @@ def test_device_frames_mixed_counted_and_alpha(built, devs, null_stream):
             if null_stream:   # consumed on the frame's own stream (vrt_frame_stream)
                 fs = r.frame_stream()
                 assert fs
-                hipcopy_on(got, ptr, fs)
+                hipcopy(got, ptr, fs)
             else:
                 torch.cuda.current_stream().wait_stream(s)
                 hipcopy(got, ptr)
@@ -198,32 +199,6 @@ def test_history_reset_keeps_held_frames(built, alpha):
                 got = np.empty((h, w, 4), np.uint8)
                 hipcopy(got, ptrs[j])
                 assert np.array_equal(got, refs[j]), f"frame {j} read after frame {i}"
-
-
-def hipcopy_on(dst: np.ndarray, ptr: int, stream_handle: int):
-    """Device -> host copy of a raw device pointer enqueued on a raw HIP stream (the frame's own
-    stream), then a wait for that stream."""
-    class View:
-        __cuda_array_interface__ = {"shape": dst.shape, "typestr": "|u1", "data": (ptr, False),
-                                    "version": 3}
-
-    ext = torch.cuda.ExternalStream(stream_handle)
-    with torch.cuda.stream(ext):
-        t = torch.as_tensor(View(), device="cuda").to("cpu", non_blocking=False)
-    ext.synchronize()
-    dst[...] = t.numpy()
-
-
-def hipcopy(dst: np.ndarray, ptr: int):
-    """Device -> host copy of a raw device pointer, viewed as a torch tensor through
-    __cuda_array_interface__."""
-
-    class View:
-        __cuda_array_interface__ = {"shape": dst.shape, "typestr": "|u1", "data": (ptr, False),
-                                    "version": 3}
-
-    torch.cuda.synchronize()
-    dst[...] = torch.as_tensor(View(), device="cuda").cpu().numpy()
 
 
 def test_headless_app_gets_the_bench_frame_time(built, tmp_path):

@@ -13,10 +13,10 @@ import pytest
 
 import oracle
 import voxelraytracer_amd as vrt
+from harness import COLOR_TOL, compare, ref_atlas
 
 pytestmark = pytest.mark.gpu
 
-COLOR_TOL = 1e-4
 THREADS = min(16, os.cpu_count() or 1)   # the GPU box's CPU share
 
 
@@ -25,18 +25,6 @@ def renderer(built):
     r = vrt.Renderer(0)
     yield r
     r.close()
-
-
-def compare(rgba_g, hits_g, cnt_g, rgba_o, hits_o, cnt_o):
-    assert np.array_equal(hits_g["voxel_index"], hits_o["voxel_index"])
-    assert np.array_equal(hits_g["ray_length"].view(np.uint32), hits_o["ray_length"].view(np.uint32))
-    assert np.array_equal(hits_g["steps"], hits_o["steps"])
-    assert np.array_equal(hits_g["flags"], hits_o["flags"])
-    for k in oracle.COUNTER_NAMES:
-        assert cnt_g[k] == cnt_o[k], k
-    d = np.abs(np.clip(rgba_g[..., :3], 0, 1) - np.clip(rgba_o[..., :3], 0, 1))
-    assert d.max() <= COLOR_TOL, float(d.max())
-    assert np.all(rgba_g[..., 3] == 1.0)
 
 
 def run_both(renderer, scene, n, w, h, refl, transp, **kw):
@@ -158,13 +146,6 @@ def test_parity_textured_full_size_refraction(renderer):
     rgba_g, hits_g, st = renderer.render(cam, p)
     rgba_o, hits_o, cnt_o = oracle.render(cam, vox, 128, p, threads=THREADS)
     compare(rgba_g, hits_g, st, rgba_o, hits_o, cnt_o)
-
-
-def ref_atlas():
-    """The reference's own textures (res/textures/*128.png, main.cpp:187-193) decoded into the
-    ABI atlas layout: tests/golden/atlas/atlas_ref128.npz (tests/golden/make_atlas_ref.py)."""
-    path = os.path.join(os.path.dirname(__file__), "golden", "atlas", "atlas_ref128.npz")
-    return np.load(path, allow_pickle=False)["atlas"]
 
 
 @pytest.mark.parametrize("scene,R,T", [("refraction", 4, 4), ("glass_cube", 1, 2)])

@@ -13,104 +13,28 @@ import pytest
 
 import oracle
 import voxelraytracer_amd as vrt
-from oracle import numpy_oracle
+from harness import float_bits as bits
+from ray_oracle import N, assert_nearest_matches, march_all, numpy_march, numpy_shadow, ray_list
 from voxelraytracer_amd import abi
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-N = 16
 COUNT = 4099          # not a multiple of 64 or 256: the last wave is partial
 NUMPY_COUNT = 300     # rays also held against the NumPy oracle (flags; occlusion)
 SCENES = ("terrain", "glass_cube", "refraction")
-F = np.float32
-
-
-def unit(d):
-    d = np.asarray(d, np.float32)
-    return d / np.sqrt((d * d).sum(axis=-1, keepdims=True), dtype=np.float32)
 
 
 @functools.lru_cache(maxsize=None)
 def scene_rays(scene):
-    """The scene's bytes and its COUNT rays: origins uniform in [-4, N + 4]^3; three of every four rays
-    aimed at a uniform point of the volume, every fourth with an unaimed Gaussian direction (aimed rays
-    alone never miss the glass cube's walls); directions normalised in float32; max_length 100, but
-    uniform in [0.5, 12] for every eighth ray (among the aimed ones)."""
-    rng = np.random.default_rng(SCENES.index(scene) + 1)
-    vox = vrt.build_scene(scene, N)
-    origins = rng.uniform(-4.0, N + 4.0, (COUNT, 3)).astype(np.float32)
-    targets = rng.uniform(0.0, N, (COUNT, 3)).astype(np.float32)
-    dirs = targets - origins
-    unaimed = np.arange(COUNT) % 4 == 3
-    dirs[unaimed] = rng.standard_normal((COUNT, 3)).astype(np.float32)[unaimed]
-    dirs = unit(dirs)
-    max_len = np.full(COUNT, 100.0, np.float32)
-    short = np.arange(COUNT) % 8 == 0
-    max_len[short] = rng.uniform(0.5, 12.0, COUNT).astype(np.float32)[short]
-    rays = vrt.make_rays(origins, dirs, max_len)
-    rays.setflags(write=False)
-    return vox, rays
-
-
-def march_all(vox, rays, max_len=None):
-    """oracle.march_one per ray -> dict of arrays (found, vidx, len, point, normal, steps)."""
-    n = len(rays)
-    out = dict(found=np.zeros(n, bool), vidx=np.zeros(n, np.int32), len=np.zeros(n, np.float32),
-               point=np.zeros((n, 3), np.float32), normal=np.zeros((n, 3), np.float32), steps=np.zeros(n, np.uint32))
-    for i, r in enumerate(rays):
-        m = oracle.march_one(vox, N, r["origin"], r["dir"], float(r["max_length"]) if max_len is None else max_len)
-        for key in out:
-            out[key][i] = m[key]
-    return out
+    """The scene's bytes and its COUNT rays (ray_oracle.ray_list's distribution)."""
+    return vrt.build_scene(scene, N), ray_list(SCENES.index(scene) + 1, COUNT)
 
 
 @functools.lru_cache(maxsize=None)
 def oracle_nearest(scene):
     vox, rays = scene_rays(scene)
     return march_all(vox, rays)
-
-
-def tracer(vox, max_len):
-    p = vrt.default_params(1, 2)
-    return numpy_oracle.Tracer(vox, N, dict(sun_dir=list(p.sun_dir), time=p.time, ray_noise=0.0, reflection_noise=0.0,
-                                            refraction_noise=0.0, max_ray_length=max_len, max_reflections=1,
-                                            max_transparencies=2, color_only=1))
-
-
-def numpy_ray(r):
-    return dict(pos=tuple(F(x) for x in r["origin"]), dir=tuple(F(x) for x in r["dir"]), len=F(0.0), energy=F(1.0),
-                voxel=0, r=0, t=0)
-
-
-def numpy_march(vox, r):
-    """Tracer.march of one vrt_ray record -> (hit dict, steps, flags)."""
-    st = dict(steps=0, flags=0)
-    hit = tracer(vox, F(r["max_length"])).march(numpy_ray(r), st)
-    return hit, st["steps"], st["flags"]
-
-
-def numpy_shadow(vox, r):
-    st = dict(steps=0, flags=0)
-    blocked = tracer(vox, F(r["max_length"])).march_shadow(numpy_ray(r), st)
-    return bool(blocked), st["steps"], st["flags"]
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def assert_nearest_matches(hits, want, vox, rays):
-    found = hits["voxel_index"] >= 0
-    assert np.array_equal(found, want["found"])
-    assert np.array_equal(hits["voxel_index"], np.where(want["found"], want["vidx"], -1))
-    assert np.array_equal(hits["steps"], want["steps"])
-    assert np.array_equal(bits(hits["ray_length"]), bits(want["len"]))
-    assert np.array_equal(bits(hits["point"]), bits(want["point"]))
-    assert np.array_equal(vrt.hit_normal(hits), want["normal"].astype(np.int8))
-    assert np.array_equal((hits["face"][found] >> 8) & 0xFF, vox[hits["voxel_index"][found]])
-    assert np.all(hits["face"][found] >> 16 == 0) and np.all(hits["face"][~found] == 0)
-    assert np.all(hits["flags"] & ~np.uint32(abi.VRT_HIT_FLAG_TIE3 | abi.VRT_HIT_FLAG_STEP_CAP) == 0)
 
 
 def assert_matches_numpy(hit_rec, vox, ray):

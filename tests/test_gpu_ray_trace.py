@@ -1,7 +1,7 @@
 """Shaded ray queries (GPU): vrt_trace_rays / vrt_trace_rays_async / vrt_trace_pixels run fragment main
 (exact_pixel with exact walks only) for a list of rays or pixels.
 
-Arbitrary rays are held against numpy_oracle.Tracer: oracle_trace() below restates the loop of
+Arbitrary rays are held against numpy_oracle.Tracer: tests/ray_oracle.py's oracle_trace() restates the loop of
 Tracer.pixel (the stack, the STACK_FULL rule, the first pop's record) for a given first ray over
 Tracer's own methods, with a Tracer per distinct max_length. voxel_index, steps and flags are equal,
 ray_length is bit-equal, the colour is within COLOR_TOL = 1e-4 (tests/test_gpu_parity.py) after the
@@ -20,44 +20,18 @@ import pytest
 
 import oracle
 import voxelraytracer_amd as vrt
+from harness import float_bits as bits, same_bytes
 from oracle import numpy_oracle
+from ray_oracle import NOISE, ONE, F, N, Z, assert_matches_oracle, make_params, oracle_records, ray_list, tracer
 from voxelraytracer_amd import abi
 
 pytestmark = pytest.mark.gpu
 
-N = 16
 COUNT = 300
 ASYNC_COUNT = 4099     # not a multiple of 64: the last wave is partial
 W, H = 96, 54
 SCENES = ("terrain", "glass_cube", "refraction")
 BOUNCES = ((1, 2), (4, 4))
-NOISE = {"noisy": (0.05, 0.01), "clean": (0.0, 0.0)}
-COLOR_TOL = 1e-4       # tests/test_gpu_parity.py
-F = np.float32
-Z, ONE = F(0.0), F(1.0)
-
-
-def unit(d):
-    d = np.asarray(d, np.float32)
-    return d / np.sqrt((d * d).sum(axis=-1, keepdims=True), dtype=np.float32)
-
-
-def ray_list(seed, count, n=N):
-    """The distribution of tests/test_gpu_ray_query.py::scene_rays: origins uniform in [-4, n + 4]^3; three
-    of every four rays aimed at a uniform point of the volume, every fourth with an unaimed Gaussian
-    direction; directions normalised in float32; max_length 100, but uniform in [0.5, 12] for every eighth."""
-    rng = np.random.default_rng(seed)
-    origins = rng.uniform(-4.0, n + 4.0, (count, 3)).astype(np.float32)
-    targets = rng.uniform(0.0, n, (count, 3)).astype(np.float32)
-    dirs = targets - origins
-    unaimed = np.arange(count) % 4 == 3
-    dirs[unaimed] = rng.standard_normal((count, 3)).astype(np.float32)[unaimed]
-    max_len = np.full(count, 100.0, np.float32)
-    short = np.arange(count) % 8 == 0
-    max_len[short] = rng.uniform(0.5, 12.0, count).astype(np.float32)[short]
-    rays = vrt.make_rays(origins, unit(dirs), max_len)
-    rays.setflags(write=False)
-    return rays
 
 
 @functools.lru_cache(maxsize=None)
@@ -68,106 +42,9 @@ def scene_rays(scene):
 
 
 @functools.lru_cache(maxsize=None)
-def atlas():
-    a = vrt.make_atlas()
-    a.setflags(write=False)
-    return a
-
-
-def make_params(bounces, noise="clean", textured=False, **kw):
-    refl, refr = NOISE[noise]
-    p = vrt.default_params(*bounces, reflection_noise=refl, refraction_noise=refr, time=3.0, **kw)
-    return vrt.textured_params(p, atlas()) if textured else p
-
-
-def tracer(vox, p, max_len):
-    d = dict(sun_dir=list(p.sun_dir), time=p.time, ray_noise=p.ray_noise, reflection_noise=p.reflection_noise,
-             refraction_noise=p.refraction_noise, max_ray_length=max_len, max_reflections=p.max_reflections,
-             max_transparencies=p.max_transparencies, color_only=p.color_only)
-    if not p.color_only:
-        d.update(atlas=atlas(), atlas_size=p.atlas_size, atlas_texture_size=p.atlas_texture_size)
-    return numpy_oracle.Tracer(vox, N, d)
-
-
-def oracle_trace(tr, origin, direction):
-    """The loop of Tracer.pixel (numpy_oracle.py:375-396) from stack[0] = Ray(origin, direction, 0, 1, air,
-    0, 0): (colour, first pop's (voxel, length), steps and flags, secondary rays popped)."""
-    stats = dict(steps=0, flags=0)
-    color = (Z, Z, Z)
-    stack = [dict(pos=tuple(F(x) for x in origin), dir=tuple(F(x) for x in direction), len=Z, energy=ONE,
-                  voxel=0, r=0, t=0)]
-    cap = tr.R + tr.T + 1
-    first, rec, pops = True, (-1, Z), 0
-    while stack:
-        ray = stack.pop()
-        if not first:
-            pops += 1
-        hit, color = tr.trace_with_shadow(ray, color, stats)
-        if first:
-            if hit["found"]:
-                rec = (hit["vidx"], hit["len"])
-            first = False
-        if hit["found"]:
-            mat = tr.mats[min(hit["voxel"], 3)]
-            if mat[2] and ray["r"] < tr.R:
-                if len(stack) < cap:
-                    stack.append(tr.reflection_ray(ray, hit))
-                else:
-                    stats["flags"] |= 4
-            if mat[1] and ray["t"] < tr.T and tr.color(hit)[3] != ONE:
-                if len(stack) < cap:
-                    stack.append(tr.refraction_ray(ray, hit))
-                else:
-                    stats["flags"] |= 4
-    return color, rec, stats, pops
-
-
-def oracle_records(vox, rays, p):
-    """oracle_trace of every ray -> (RAY_COLOR_DTYPE records, secondary rays popped per ray)."""
-    out = np.zeros(len(rays), abi.RAY_COLOR_DTYPE)
-    pops = np.zeros(len(rays), np.int64)
-    tracers = {}
-    with np.errstate(all="ignore"):
-        for i, r in enumerate(rays):
-            ml = F(r["max_length"])
-            tr = tracers.setdefault(ml.tobytes(), tracer(vox, p, ml))
-            color, rec, st, pops[i] = oracle_trace(tr, r["origin"], r["dir"])
-            out[i] = (rec[0], rec[1], st["steps"], st["flags"], (color[0], color[1], color[2], 1.0))
-    return out, pops
-
-
-@functools.lru_cache(maxsize=None)
 def scene_oracle(scene, bounces, noise, textured=False):
     vox, rays = scene_rays(scene)
     return oracle_records(vox, rays, make_params(bounces, noise, textured))
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def store_clamp(c):
-    """The framebuffer store's clamp to [0, 1], NaN -> 0 (numpy_oracle.unorm8)."""
-    return np.fmin(np.fmax(np.asarray(c, np.float32), F(0.0)), F(1.0))
-
-
-def assert_matches_oracle(got, want, what=""):
-    assert got.dtype == np.dtype(abi.RAY_COLOR_DTYPE) and got.shape == want.shape
-    assert np.array_equal(got["voxel_index"], want["voxel_index"]), what
-    assert np.array_equal(got["steps"], want["steps"]), what
-    assert np.array_equal(got["flags"], want["flags"]), what
-    assert np.array_equal(bits(got["ray_length"]), bits(want["ray_length"])), what
-    g, w = got["rgba"][:, :3], want["rgba"][:, :3]
-    assert np.array_equal(np.isnan(g), np.isnan(w)), what
-    diff = np.abs(store_clamp(g).astype(np.float64) - store_clamp(w).astype(np.float64)).max()
-    print(f"{what}: max |clamped colour difference| {diff:.3e}")
-    assert diff <= COLOR_TOL, what
-    assert np.all(got["rgba"][:, 3] == 1.0), what
-
-
-def same_bytes(a, b):
-    return np.array_equal(np.ascontiguousarray(a).view(np.uint8).reshape(-1),
-                          np.ascontiguousarray(b).view(np.uint8).reshape(-1))
 
 
 # ---- 1. arbitrary rays against the NumPy oracle ------------------------------------------------

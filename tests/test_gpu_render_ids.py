@@ -8,8 +8,10 @@ import functools
 import numpy as np
 import pytest
 
+import harness
 import oracle
 import voxelraytracer_amd as vrt
+from harness import all_pixels, assert_ids_equal_pick, depth_restated, edge_cameras
 from voxelraytracer_amd import abi
 
 pytestmark = pytest.mark.gpu
@@ -26,22 +28,12 @@ def scene(name, n=N):
     return v
 
 
-def all_pixels(w, h):
-    y, x = np.meshgrid(np.arange(h), np.arange(w), indexing="ij")
-    return np.stack([x.reshape(-1), y.reshape(-1)], axis=1).astype(np.int32)
-
-
 def params(ray_noise=0.0):
     return vrt.default_params(1, 2, ray_noise=ray_noise)
 
 
 def pick_frame(r, cam, p):
     return r.pick(cam, p, all_pixels(cam.width, cam.height)).reshape(cam.height, cam.width)
-
-
-def assert_ids_equal_pick(ids, picks, what=""):
-    bad = np.argwhere((ids["voxel_index"] != picks["voxel_index"]) | (ids["face"] != picks["face"]))
-    assert bad.size == 0, (what, len(bad), bad[:5].tolist())
 
 
 @functools.lru_cache(maxsize=None)
@@ -52,28 +44,9 @@ def oracle_hits(name, n, ray_noise):
 
 @functools.lru_cache(maxsize=None)
 def primary_rays(n, ray_noise):
-    """pos and dir of every pixel's primary ray as it entered RayMarch: oracle.trace_pixel's first record
-    (tests/test_gpu_ray_query.py::primary_ray). The ray depends on the volume through its size alone
-    (pos = near-plane point + n / 2)."""
-    cam, p, vox = vrt.make_camera(W, H), params(ray_noise), scene("terrain", n)
-    pos, dirs = np.zeros((H, W, 3), np.float32), np.zeros((H, W, 3), np.float32)
-    for py in range(H):
-        for px in range(W):
-            recs, _ = oracle.trace_pixel(cam, vox, n, p, px, py, cap=4)
-            assert recs[0, 0] == 1 and recs[0, 15] == 0 and recs[0, 16] == 1
-            pos[py, px], dirs[py, px] = recs[0, 9:12], recs[0, 12:15]
-    return pos, dirs
-
-
-def depth_restated(picks, pos, dirs):
-    """(np.rint(point[a]) - pos[a]) / dir[a] in float32, a the face's axis; +inf for a miss."""
-    a = (picks["face"] & 3).astype(np.intp)[..., None]
-    pt = np.take_along_axis(picks["point"], a, -1)[..., 0]
-    pa, da = np.take_along_axis(pos, a, -1)[..., 0], np.take_along_axis(dirs, a, -1)[..., 0]
-    with np.errstate(all="ignore"):
-        d = ((np.rint(pt) - pa) / da).astype(np.float32)
-    assert (np.rint(pt) - pa).dtype == np.float32 and da.dtype == np.float32
-    return np.where(picks["voxel_index"] >= 0, d, np.float32(np.inf)).astype(np.float32)
+    """pos and dir of every pixel's primary ray as it entered RayMarch (harness.primary_rays). The ray depends
+    on the volume through its size alone (pos = near-plane point + n / 2)."""
+    return harness.primary_rays(vrt.make_camera(W, H), scene("terrain", n), n, params(ray_noise))
 
 
 # ---- 5, 6: IDs against the pick and the oracle, the depth ---------------------------------------
@@ -227,10 +200,8 @@ def test_async_pass_is_capturable(built):
 
 @pytest.mark.parametrize("name", SCENES)
 def test_edge_cameras(built, name):
-    """The 118 cameras within a cell of the volume's faces and corners (tests/test_gpu_cert_lean.py):
+    """The 118 cameras within a cell of the volume's faces and corners (harness.edge_cameras):
     IDs equal the pick at every pixel."""
-    from test_gpu_cert_lean import edge_cameras
-
     w, h = 40, 24
     p = params()
     cams = edge_cameras(N, w, h)

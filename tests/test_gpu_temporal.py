@@ -14,10 +14,9 @@ import torch
 
 import oracle
 import voxelraytracer_amd as vrt
+from harness import check_raw
 
 pytestmark = pytest.mark.gpu
-
-COLOR_TOL = 1e-4
 
 
 @pytest.fixture(scope="module")
@@ -25,19 +24,6 @@ def renderer(built):
     r = vrt.Renderer(0)
     yield r
     r.close()
-
-
-def check_raw(raw_g, rgba_o):
-    """Device RGB8 bytes vs the oracle's float colour quantised by the oracle."""
-    raw_o, _ = oracle.temporal(rgba_o, np.zeros(rgba_o.shape, np.uint8), 1.0)
-    diff = raw_g[..., :3].astype(np.int16) - raw_o[..., :3].astype(np.int16)
-    bad = diff != 0
-    assert np.abs(diff).max(initial=0) <= 1
-    if bad.any():   # only where the oracle colour is within COLOR_TOL of a .5 boundary
-        x = np.clip(rgba_o[..., :3][bad], 0, 1).astype(np.float64) * 255.0
-        assert np.all(np.abs(x - np.floor(x) - 0.5) <= COLOR_TOL * 255.0)
-    assert np.all(raw_g[..., 3] == 255)
-    return int(bad.sum())
 
 
 def scene(renderer, name, n, w, h, R, T, **kw):

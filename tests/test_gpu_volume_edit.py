@@ -13,12 +13,12 @@ import pytest
 
 import oracle
 import voxelraytracer_amd as vrt
+from harness import COLOR_TOL, assert_same_packed
 from skipfield_reference import apply_edit, packed_reference, random_edit
 from voxelraytracer_amd import abi
 
 pytestmark = pytest.mark.gpu
 
-COLOR_TOL = 1e-4   # the project's colour tolerance against the oracle (tests/test_gpu_parity.py)
 THREADS = min(16, os.cpu_count() or 1)
 
 
@@ -66,15 +66,6 @@ def fresh_packed(vox, n, layout=0):
         f.set_skip_layout(layout)
         f.upload_volume(vox, n)
         return f.debug_packed_volume()
-
-
-def assert_same_packed(got, want):
-    assert got.shape == want.shape
-    if not np.array_equal(got, want):
-        bad = np.argwhere(got != want)
-        raise AssertionError(f"{len(bad)} packed texels differ, first [octant, z, y, x] = {bad[:4].tolist()}: "
-                             f"{[hex(int(got[tuple(b)])) for b in bad[:4]]} != "
-                             f"{[hex(int(want[tuple(b)])) for b in bad[:4]]}")
 
 
 @pytest.mark.parametrize("scene", ["terrain", "glass_cube"])

@@ -3,25 +3,16 @@ adversarial volumes (tests/adversarial_volumes.py) at 8^3: material bytes up to 
 filled faces, the solid, all-glass and empty volumes and the glass / grass lattice, from four cameras
 inside the volume, colour-only and textured. The contract is tests/test_oracle_crosscheck.py's: hit
 records and counters equal, colour within 1e-5 (only exp2 / log2 differ: glibc against NumPy)."""
-import functools
-
 import numpy as np
 import pytest
 
 import oracle
 import voxelraytracer_amd as vrt
 from adversarial_volumes import INSIDE, NAMES, base_params, camera, volumes
+from harness import params_dict, synthetic_atlas
 from oracle import numpy_oracle
-from test_oracle_crosscheck import params_dict
 
 N, W, H = 8, 20, 14
-
-
-@functools.lru_cache(maxsize=None)
-def atlas():
-    a = vrt.make_atlas(32, 16)
-    a.setflags(write=False)
-    return a
 
 
 @pytest.mark.parametrize("textured", [False, True], ids=["colour", "textured"])
@@ -32,7 +23,7 @@ def test_c_oracle_matches_numpy_on_adversarial_volumes(built, name, cid, texture
     cam = camera(N, cid, W, H)
     p = base_params()
     if textured:
-        p = vrt.textured_params(p, atlas(), 16)
+        p = vrt.textured_params(p, synthetic_atlas(32, 16), 16)
     rgba_c, hits_c, cnt_c = oracle.render(cam, vox, N, p, threads=1)
     rgba_n, hits_n, cnt_n = numpy_oracle.render(list(cam.inv_pv), W, H, vox, N, params_dict(p))
     assert np.array_equal(hits_c["voxel_index"], hits_n["voxel_index"])

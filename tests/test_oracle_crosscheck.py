@@ -7,6 +7,7 @@ import pytest
 
 import oracle
 import voxelraytracer_amd as vrt
+from harness import params_dict
 from oracle import numpy_oracle
 
 CASES = [
@@ -24,17 +25,6 @@ CASES = [
     ("glass_cube", 16, 15, 15, 4, 4, dict(pos=(0.25, 0.25, 0.25), rot=(-35.26439, 45.0, 0.0))),
     ("glass_cube", 16, 48, 32, 1, 2, {}),
 ]
-
-
-def params_dict(p):
-    d = dict(sun_dir=list(p.sun_dir), time=p.time, ray_noise=p.ray_noise,
-             reflection_noise=p.reflection_noise, refraction_noise=p.refraction_noise,
-             max_ray_length=p.max_ray_length, max_reflections=p.max_reflections,
-             max_transparencies=p.max_transparencies, color_only=p.color_only)
-    if not p.color_only:
-        d.update(atlas=p._atlas_ref, atlas_size=p.atlas_size,
-                 atlas_texture_size=p.atlas_texture_size)
-    return d
 
 
 @pytest.mark.parametrize("case", CASES, ids=[f"{c[0]}{c[1]}_{i}" for i, c in enumerate(CASES)])
