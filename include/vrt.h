@@ -231,8 +231,8 @@ int vrt_certified(const vrt_ctx* ctx);
 
 /* ABI v8 (r02): device timestamps of the async band launches (vrt_render_rows*_async,
  * vrt_render_temporal_rows*_async on the first device) and of the ray-query launches (vrt_cast_rays*,
- * vrt_pick_pixels, vrt_trace_rays*, vrt_trace_pixels, vrt_render_ids*, vrt_reproject_temporal_async: one
- * launch per call):
+ * vrt_pick_pixels, vrt_trace_rays*, vrt_trace_pixels, vrt_render_ids*, vrt_reproject_temporal_async,
+ * vrt_reproject_temporal_fetch_async: one launch per call):
  * vrt_set_launch_timing(ctx, n) creates
  * timing events for the next n launches (0: off; it synchronises the first device when replacing
  * earlier events), each launch then records its kernel's start and end on the device
@@ -566,13 +566,57 @@ int vrt_reproject_temporal_async(vrt_ctx* ctx, const vrt_camera* cam, const vrt_
  * size, after vrt_reprojected_history_reset, or after a frame whose camera matrix has no inverse.
  * stats (optional): kernel_ms is the GPU time from the first launch's start to the last launch's end;
  * counters (VRT_STATS_COUNTERS) are VRT_ERR_UNSUPPORTED.
- * Limits: the fetch is nearest, so a history that is resampled frame after frame drifts by up to half a
- * pixel per frame; the exact ID pass runs inside every call. */
+ * Limits: the default fetch is nearest, so a history that is resampled frame after frame drifts by up to
+ * half a pixel per frame (vrt_set_reprojected_fetch selects the bilinear fetch); the exact ID pass runs inside
+ * every call. */
 int vrt_render_frame_reprojected(vrt_ctx* ctx, const vrt_camera* cam, const vrt_params* params, float alpha,
                                  uint8_t* out_rgba8, vrt_stats* stats);
 
 /* The next vrt_render_frame_reprojected has no history: its output is its raw frame. */
 int vrt_reprojected_history_reset(vrt_ctx* ctx);
+
+/* ---- bilinear history fetch (added within v15: detect by symbol lookup) ----------------------- */
+/* The history fetch of the reprojected filter as a mode. VRT_FETCH_NEAREST is the filter above.
+ * VRT_FETCH_BILINEAR fetches the four texels around the reprojected position and keeps those that show the
+ * pixel's own voxel face: a history resampled frame after frame no longer jitters by half a pixel, and a
+ * pixel whose nearest texel shows another face keeps the history of its neighbours that do not. */
+enum { VRT_FETCH_NEAREST = 0, VRT_FETCH_BILINEAR = 1 };
+
+/* vrt_reproject_temporal_async with a fetch mode and an optional tap mask. Everything said there about the
+ * arguments holds here: band indexing, the pitches, the aliasing rule, the errors, rows == 0 as a successful
+ * no-op, a failed call writes nothing; one kernel launch on hip_stream (one launch for vrt_set_launch_timing),
+ * no memset, no allocation, no atomics, no context-owned state, capturable. In addition an unknown fetch is
+ * VRT_ERR_INVALID, and d_taps (optional) is one byte per pixel at [i * pitch + px], of any alignment.
+ * VRT_FETCH_NEAREST: d_out_rgba8 and d_src are vrt_reproject_temporal_async's bytes (without d_taps it is
+ * the same kernel); d_taps is 1 for an accepted pixel, else 0.
+ * VRT_FETCH_BILINEAR, per pixel, in float32 and in exactly this order (no contraction, correctly rounded
+ * division): steps 1-6 above, which give sx, sy and the codes -4, -2 and -1 with the same precedence; then
+ *   7. tx = sx - 0.5f, x0 = floorf(tx), fx = tx - x0, ix0 = int(x0); ty, y0, fy, iy0 likewise (texel centres
+ *      sit at +0.5; ix0 may be -1 and ix0 + 1 may be width, rows likewise);
+ *   8. tap k = 0..3 at (ix0 + (k & 1), iy0 + (k >> 1)), with the weights w0 = (1 - fx) * (1 - fy),
+ *      w1 = fx * (1 - fy), w2 = (1 - fx) * fy, w3 = fx * fy;
+ *   9. tap k is valid iff its coordinates lie in [0, width) x [0, height), w_k > 0, and both words of
+ *      d_prev_ids there equal the pixel's d_ids record; a tap outside the previous image is never loaded;
+ *  10. wsum = ((v0 + v1) + v2) + v3 with v_k = valid ? w_k : 0; no valid tap: code -3, the raw pixel;
+ *  11. else accepted; per channel, with c_k the tap's byte / 255 (correctly rounded):
+ *      h = (((v0 * c0 + v1 * c1) + v2 * c2) + v3 * c3) / wsum,
+ *      out = unorm8(alpha * (raw byte / 255) + (1.0f - alpha) * h), A = 255: the history is filtered once
+ *      and the colour quantised once;
+ *  12. d_src = qy * width + qx with (qx, qy) = floor(sx, sy), the nearest texel, which is one of the four
+ *      taps (valid or not); d_taps = the mask of valid taps, bit k for tap k, 0 for a pixel not accepted.
+ * With an unmoved camera this mode is NOT byte-equal to vrt_render_frame's filter: the float round trip leaves
+ * fx and fy within about 1e-3 of 0 or 1, so the neighbours enter with tiny weights. */
+int vrt_reproject_temporal_fetch_async(vrt_ctx* ctx, const vrt_camera* cam, const vrt_params* params,
+                                       const float prev_pv[16], float alpha, int32_t fetch, int32_t row0,
+                                       int32_t rows, int32_t pitch, const uint32_t* d_raw_rgba8,
+                                       const vrt_pixel_id* d_ids, const float* d_depth,
+                                       const uint32_t* d_prev_rgba8, const vrt_pixel_id* d_prev_ids,
+                                       int32_t prev_pitch, uint32_t* d_out_rgba8, int32_t* d_src, uint8_t* d_taps,
+                                       void* hip_stream);
+
+/* The fetch mode of vrt_render_frame_reprojected's filter; VRT_FETCH_NEAREST in a new context. The history
+ * (frames, IDs, matrix) is kept across a switch. An unknown mode is VRT_ERR_INVALID and changes nothing. */
+int vrt_set_reprojected_fetch(vrt_ctx* ctx, int32_t fetch);
 
 /* ---- textured mode (voxel.glsl without _COLOR_ONLY) --------------------- */
 /* With vrt_params.color_only = 0 the kernel shades with the textured material table

@@ -15,6 +15,8 @@ import numpy as np
 from . import abi
 from .abi import (  # noqa: F401  (re-exported vocabulary)
     COUNTER_NAMES,
+    FETCH_BILINEAR,
+    FETCH_NEAREST,
     HIT_DTYPE,
     PIXEL_ID_DTYPE,
     RAY_COLOR_DTYPE,
@@ -490,6 +492,27 @@ class Renderer:
             self._h, C.byref(cam), C.byref(params), pv.ctypes.data, alpha, row0, rows, pitch, d_raw or None,
             d_ids or None, d_depth or None, d_prev or None, d_prev_ids or None, prev_pitch, d_out or None,
             d_src or None, stream or None), "vrt_reproject_temporal_async")
+
+    def reproject_temporal_fetch_async(self, cam: Camera, params: Params, prev_pv, alpha: float, fetch: int, row0: int,
+                                       rows: int, pitch: int, d_raw: int, d_ids: int, d_depth: int, d_prev: int,
+                                       d_prev_ids: int, prev_pitch: int, d_out: int, d_src: int = 0, d_taps: int = 0,
+                                       stream: int = 0):
+        """vrt_reproject_temporal_fetch_async: reproject_temporal_async with a history fetch mode, FETCH_NEAREST
+        (that method's bytes) or FETCH_BILINEAR (the four texels around the reprojected position, each used
+        only if it shows the pixel's own voxel face). d_src receives the nearest texel's index or the code,
+        as there; d_taps (0: none) one byte per pixel at `pitch`, any alignment: the mask of the taps used
+        (bit k: tap (x0 + (k & 1), y0 + (k >> 1))), 1 for a pixel the nearest fetch accepts, 0 for a pixel
+        that is not accepted."""
+        pv = np.ascontiguousarray(prev_pv, dtype=np.float32).reshape(16)
+        self._check(self._lib.vrt_reproject_temporal_fetch_async(
+            self._h, C.byref(cam), C.byref(params), pv.ctypes.data, alpha, fetch, row0, rows, pitch, d_raw or None,
+            d_ids or None, d_depth or None, d_prev or None, d_prev_ids or None, prev_pitch, d_out or None,
+            d_src or None, d_taps or None, stream or None), "vrt_reproject_temporal_fetch_async")
+
+    def set_reprojected_fetch(self, mode: int):
+        """vrt_set_reprojected_fetch: the history fetch of render_frame_reprojected's filter, FETCH_NEAREST (the
+        default) or FETCH_BILINEAR; the history is kept across a switch."""
+        self._check(self._lib.vrt_set_reprojected_fetch(self._h, mode), "vrt_set_reprojected_fetch")
 
     def render_frame_reprojected(self, cam: Camera, params: Params, alpha: float, timing: bool = False):
         """vrt_render_frame_reprojected: the frame loop with the reprojected temporal filter and a history of

@@ -148,6 +148,10 @@ class PixelId(C.Structure):
 # numpy dtype of one vrt_pixel_id record (vrt_ray_hit's fields of the same names)
 PIXEL_ID_DTYPE = [("voxel_index", "<i4"), ("face", "<u4")]
 
+# history fetch of the reprojected temporal filter (vrt_reproject_temporal_fetch_async, vrt_set_reprojected_fetch)
+FETCH_NEAREST = 0
+FETCH_BILINEAR = 1
+
 # name -> (restype, argtypes): every function include/vrt.h declares
 # entry points added after ABI v12 (an older build loaded by VRT_LIB with VRT_LIB_ABI=<its version>
 # may lack exactly these)
@@ -162,7 +166,9 @@ ADDED_IN = {"vrt_render_temporal_batch_async": 14, "vrt_set_cert_trees": 15,
             "vrt_render_ids_async": 16, "vrt_render_ids": 16, "vrt_ids_deferred": 16,
             # added within v15 after the ID and depth pass (reprojected temporal filter)
             "vrt_camera_forward": 16, "vrt_reproject_temporal_async": 16, "vrt_render_frame_reprojected": 16,
-            "vrt_reprojected_history_reset": 16}
+            "vrt_reprojected_history_reset": 16,
+            # added within v15 after the reprojected filter (bilinear history fetch)
+            "vrt_reproject_temporal_fetch_async": 16, "vrt_set_reprojected_fetch": 16}
 
 SIGNATURES = {
     "vrt_abi_version": (C.c_int, []),
@@ -221,6 +227,12 @@ SIGNATURES = {
     "vrt_render_frame_reprojected": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.c_float,
                                                C.c_void_p, C.POINTER(Stats)]),
     "vrt_reprojected_history_reset": (C.c_int, [C.c_void_p]),
+    # added within v15 (detect by symbol lookup): bilinear history fetch
+    "vrt_reproject_temporal_fetch_async": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.c_void_p,
+                                                     C.c_float, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vrt_set_reprojected_fetch": (C.c_int, [C.c_void_p, C.c_int32]),
     "vrt_build_scene_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p]),
     "vrt_debug_packed_volume": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
     "vrt_debug_collectives": (C.c_int, [C.c_void_p]),

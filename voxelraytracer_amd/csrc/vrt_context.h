@@ -218,6 +218,7 @@ struct vrt_ctx {
   int32_t rp_w = 0, rp_h = 0;
   int rp_cur = 0;
   bool rp_valid = false;
+  int32_t rp_fetch = VRT_FETCH_NEAREST;  // vrt_set_reprojected_fetch: which filter the loop launches
   float rp_pv[16] = {};
   hipEvent_t ev_rp_beg = nullptr, ev_rp_end = nullptr;
   // ABI v12: this process's rank of a one-process-per-GPU job (vrt_comm_join): one RCCL

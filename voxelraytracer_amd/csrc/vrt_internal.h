@@ -184,6 +184,12 @@ struct ReprojArgs {
 constexpr int kReprojWg = 256;
 void launch_reproject(const KArgs& a, const ReprojArgs& r, hipStream_t s, hipEvent_t ev_begin = nullptr,
                       hipEvent_t ev_end = nullptr);
+// The same launch with a fetch mode and an optional tap-mask buffer (one byte per band pixel at a.pitch):
+// VRT_FETCH_NEAREST without taps is launch_reproject itself (reproject_kernel), with taps
+// reproject_nearest_taps_kernel (the same pixels plus the byte); VRT_FETCH_BILINEAR is
+// reproject_bilinear_kernel. One launch either way; fetch is one of the two modes (the caller checks)
+void launch_reproject_fetch(const KArgs& a, const ReprojArgs& r, int32_t fetch, uint8_t* taps, hipStream_t s,
+                            hipEvent_t ev_begin = nullptr, hipEvent_t ev_end = nullptr);
 // fold the counter replicas into dst (accumulating) and re-zero them
 void launch_reduce_counters(unsigned long long* rep, unsigned long long* dst, hipStream_t s);
 // in-place edit of the box [lo, lo + ext) (vrt_update_volume_region), inside [0, N)^3:

@@ -199,12 +199,13 @@ static int check_reproject(vrt_ctx* ctx, const vrt_camera* cam, const float* pre
 }
 
 // One reprojection launch over rows [row0, row0 + rows) (rows >= 1) on `st`: no allocation, no host
-// synchronisation. eb / ee: the launch's device timestamps (optional)
+// synchronisation. eb / ee: the launch's device timestamps (optional). fetch, d_taps: the fetch mode and the
+// optional tap masks of vrt_reproject_temporal_fetch_async (nearest without taps: the old entry point's launch)
 static int enqueue_reproject(vrt_ctx* ctx, const vrt_camera* cam, const vrt_params* p, const float* prev_pv, float alpha,
                              int32_t row0, int32_t rows, int32_t pitch, const uint32_t* d_raw, const vrt_pixel_id* d_ids,
                              const float* d_depth, const uint32_t* d_prev, const vrt_pixel_id* d_prev_ids,
                              int32_t prev_pitch, uint32_t* d_out, int32_t* d_src, hipStream_t st, hipEvent_t eb,
-                             hipEvent_t ee) {
+                             hipEvent_t ee, int32_t fetch = VRT_FETCH_NEAREST, uint8_t* d_taps = nullptr) {
   Shard& s = ctx->sh[0];
   // the frame's argument block, as enqueue_ids fills it: primary_ray reads it
   vrt::KArgs a = make_args(ctx, s, cam, p, row0, rows, 1);
@@ -220,7 +221,7 @@ static int enqueue_reproject(vrt_ctx* ctx, const vrt_camera* cam, const vrt_para
   r.prev_ids = reinterpret_cast<const uint2*>(d_prev_ids);
   r.out = d_out;
   r.src = d_src;
-  vrt::launch_reproject(a, r, st, eb, ee);
+  vrt::launch_reproject_fetch(a, r, fetch, d_taps, st, eb, ee);
   VRT_HIP(ctx, hipGetLastError());
   return VRT_OK;
 }
@@ -240,6 +241,26 @@ int vrt_reproject_temporal_async(vrt_ctx* ctx, const vrt_camera* cam, const vrt_
   launch_timing_events(ctx, eb, ee);
   return enqueue_reproject(ctx, cam, p, prev_pv, alpha, row0, rows, pitch, d_raw_rgba8, d_ids, d_depth, d_prev_rgba8,
                            d_prev_ids, prev_pitch, d_out_rgba8, d_src, static_cast<hipStream_t>(hip_stream), eb, ee);
+}
+
+int vrt_reproject_temporal_fetch_async(vrt_ctx* ctx, const vrt_camera* cam, const vrt_params* p, const float prev_pv[16],
+                                       float alpha, int32_t fetch, int32_t row0, int32_t rows, int32_t pitch,
+                                       const uint32_t* d_raw_rgba8, const vrt_pixel_id* d_ids, const float* d_depth,
+                                       const uint32_t* d_prev_rgba8, const vrt_pixel_id* d_prev_ids, int32_t prev_pitch,
+                                       uint32_t* d_out_rgba8, int32_t* d_src, uint8_t* d_taps, void* hip_stream) {
+  if (!ctx) return VRT_ERR_INVALID;
+  int st = check_ids(ctx, cam, p, row0, rows, pitch, d_ids, d_depth, true);
+  if (st != VRT_OK) return st;
+  st = check_reproject(ctx, cam, prev_pv, prev_pitch, d_raw_rgba8, d_depth, d_prev_rgba8, d_prev_ids, d_out_rgba8,
+                       d_src);
+  if (st != VRT_OK) return st;
+  if (fetch != VRT_FETCH_NEAREST && fetch != VRT_FETCH_BILINEAR) return fail(ctx, VRT_ERR_INVALID, "unknown fetch mode");
+  if (rows == 0) return VRT_OK;
+  hipEvent_t eb, ee;
+  launch_timing_events(ctx, eb, ee);
+  return enqueue_reproject(ctx, cam, p, prev_pv, alpha, row0, rows, pitch, d_raw_rgba8, d_ids, d_depth, d_prev_rgba8,
+                           d_prev_ids, prev_pitch, d_out_rgba8, d_src, static_cast<hipStream_t>(hip_stream), eb, ee,
+                           fetch, d_taps);
 }
 
 // The staging of vrt_render_frame_reprojected on the first device (the current one), for frames of w x h:
@@ -292,7 +313,7 @@ int vrt_render_frame_reprojected(vrt_ctx* ctx, const vrt_camera* cam, const vrt_
   const bool hist = ctx->rp_valid;
   st = enqueue_reproject(ctx, cam, &geom, ctx->rp_pv, alpha, 0, h, w, ctx->d_rp_raw.p, ctx->d_rp_ids[cur].p, ctx->d_rp_depth.p,
                          hist ? ctx->d_rp_out[prev].p : nullptr, hist ? ctx->d_rp_ids[prev].p : nullptr, w,
-                         ctx->d_rp_out[cur].p, nullptr, ms, nullptr, stats ? ctx->ev_rp_end : nullptr);
+                         ctx->d_rp_out[cur].p, nullptr, ms, nullptr, stats ? ctx->ev_rp_end : nullptr, ctx->rp_fetch);
   if (st != VRT_OK) return st;
   // 4. to the host through the pinned staging
   VRT_HIP(ctx, hipMemcpyAsync(ctx->h_stage.p, ctx->d_rp_out[cur].p, bytes, hipMemcpyDeviceToHost, ms));
@@ -313,6 +334,14 @@ int vrt_render_frame_reprojected(vrt_ctx* ctx, const vrt_camera* cam, const vrt_
 int vrt_reprojected_history_reset(vrt_ctx* ctx) {
   if (!ctx) return VRT_ERR_INVALID;
   ctx->rp_valid = false;
+  return VRT_OK;
+}
+
+int vrt_set_reprojected_fetch(vrt_ctx* ctx, int32_t fetch) {
+  if (!ctx) return VRT_ERR_INVALID;
+  if (fetch != VRT_FETCH_NEAREST && fetch != VRT_FETCH_BILINEAR)
+    return fail(ctx, VRT_ERR_INVALID, "unknown fetch mode");
+  ctx->rp_fetch = fetch;  // the history (frames, IDs, matrix) stays: only the next calls' filter changes
   return VRT_OK;
 }
 

@@ -871,6 +871,17 @@ void launch_reproject(const KArgs& a, const ReprojArgs& r, hipStream_t s, hipEve
     hipLaunchKernelGGL(reproject_kernel, grid, dim3(kReprojWg), 0, s, a, r);
 }
 
+void launch_reproject_fetch(const KArgs& a, const ReprojArgs& r, int32_t fetch, uint8_t* taps, hipStream_t s,
+                            hipEvent_t ev_begin, hipEvent_t ev_end) {
+  if (fetch == VRT_FETCH_NEAREST && !taps) return launch_reproject(a, r, s, ev_begin, ev_end);
+  auto kern = fetch == VRT_FETCH_BILINEAR ? reproject_bilinear_kernel : reproject_nearest_taps_kernel;
+  const dim3 grid(uint32_t(a.width + 15) / 16u, uint32_t(a.rows + 15) / 16u);
+  if (ev_begin || ev_end)
+    hipExtLaunchKernelGGL(kern, grid, dim3(kReprojWg), 0, s, ev_begin, ev_end, 0, a, r, taps);
+  else
+    hipLaunchKernelGGL(kern, grid, dim3(kReprojWg), 0, s, a, r, taps);
+}
+
 void launch_reduce_counters(unsigned long long* rep, unsigned long long* dst, hipStream_t s) {
   hipLaunchKernelGGL(reduce_counters_kernel, dim3(1), dim3(64), 0, s, rep, dst);
 }
