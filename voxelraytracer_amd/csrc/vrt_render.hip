@@ -356,15 +356,29 @@ __device__ __forceinline__ Ray unpack_stack_ray(const StackRay& e) {
 // (cert_secondary; on glass-heavy frames their glass hits pay both walks, C1 +19 %: off there).
 // Returns whether the pixel ran a bounce stack.
 // NL: lanes per workgroup of the LDS stack bottom `lstk` (this lane's word 0).
-template <bool STATS, bool TEX, bool CSH = false, bool CSEC = false, int NL = kWgThreads>
+// LATE (the exact pass's colour instances): c comes without the sun, the sky factor and the atlas
+// (init_ctx<true>). The primary hit's shading and each iteration of the bounce loop read them, and
+// the loop the two depth limits, through the opaque view of the kernel's arguments (late_ctx,
+// late_kargs: vrt_cert.h), so that none of them is live across the primary walk or from one
+// iteration to the next: as SGPRs they were spilled into VGPR lanes the walks then lacked.
+template <bool STATS, bool TEX, bool CSH = false, bool CSEC = false, int NL = kWgThreads, bool LATE = false>
 __device__ __forceinline__ bool exact_pixel(const KArgs& a, const Ctx& c, Ray ray, f3& color,
                                             Counters& k, uint32_t& steps, uint32_t& flags,
                                             int32_t& hit_vidx, float& hit_len, float* __restrict__ lstk,
                                             float s_init = -1.0f) {
+  static_assert(!LATE || !TEX, "a textured walk reads the atlas");
   StackRay stack[kMaxStack - 2];  // the top entry lives in `ray`, the bottom one in LDS
-  const int cap = a.max_refl + a.max_transp + 1;
+  const int cap0 = LATE ? 0 : a.max_refl + a.max_transp + 1;
   int sp = 0;
-  const Hit h0 = trace_with_shadow<STATS, TEX, true, CSH>(c, ray, color, k, steps, flags, s_init);
+  Hit h0;
+  if constexpr (LATE) {
+    h0 = march<STATS, TEX, true>(c, ray, k, steps, flags, s_init);
+    Ctx lc = c;
+    late_ctx(lc);
+    shade<STATS, TEX, CSH>(lc, ray, h0, color, k, steps, flags);
+  } else {
+    h0 = trace_with_shadow<STATS, TEX, true, CSH>(c, ray, color, k, steps, flags, s_init);
+  }
   STAMP_PIXEL_BEGIN();
   hit_vidx = h0.found ? h0.vidx : -1;
   hit_len = h0.found ? h0.len : 0.0f;
@@ -372,13 +386,25 @@ __device__ __forceinline__ bool exact_pixel(const KArgs& a, const Ctx& c, Ray ra
     __builtin_amdgcn_s_setprio(kStackPrio);  // bounce stacks: the longest waves of a frame
     Hit h = h0;
     for (;;) {
-      // The sun vector and its reciprocal are opaque per iteration (an empty asm on SGPR copies),
-      // so the compiler cannot hoist the per-lane products the loop body forms from them into
-      // VGPRs live across the whole loop: those were spilled per lane on loop entry. Scratch
+      // The sun vector and its reciprocal are opaque per iteration (an empty asm on SGPR copies, or
+      // LATE's reads), so the compiler cannot hoist the per-lane products the loop body forms from
+      // them into VGPRs live across the whole loop: those were spilled per lane on loop entry. Scratch
       // 832 -> 720 B per lane, WRITE_SIZE per C3 frame 17.2 -> 14.6 MB (DESIGN.md §6 "HBM writes").
       Ctx lc = c;
-      asm volatile("" : "+s"(lc.sun_n.x), "+s"(lc.sun_n.y), "+s"(lc.sun_n.z), "+s"(lc.sun_rcp.x),
-                   "+s"(lc.sun_rcp.y), "+s"(lc.sun_rcp.z));
+      int max_refl, max_transp, cap;
+      if constexpr (LATE) {
+        late_ctx(lc);
+        LateKArgs* ka = late_kargs();
+        max_refl = ka->max_refl;
+        max_transp = ka->max_transp;
+        cap = max_refl + max_transp + 1;
+      } else {
+        asm volatile("" : "+s"(lc.sun_n.x), "+s"(lc.sun_n.y), "+s"(lc.sun_n.z), "+s"(lc.sun_rcp.x),
+                     "+s"(lc.sun_rcp.y), "+s"(lc.sun_rcp.z));
+        max_refl = a.max_refl;
+        max_transp = a.max_transp;
+        cap = cap0;
+      }
       // The reference pushes the reflection ray, then the refraction ray, then pops the top
       // (:440-448). The ray pushed last is popped at once, so it goes straight to `ray` and only a
       // reflection ray under a refraction ray is written to the scratch stack: same rays in the
@@ -387,8 +413,8 @@ __device__ __forceinline__ bool exact_pixel(const KArgs& a, const Ctx& c, Ray ra
       bool push_r = false, push_t = false;
       if (h.found) {
         const uint32_t m = mat_id(h.voxel);
-        const bool pr = mat_reflective(m) && ray.rdepth < a.max_refl;
-        const bool pt = mat_transparent(m) && ray.tdepth < a.max_transp && get_color<TEX>(lc, h).w != 1.0f;
+        const bool pr = mat_reflective(m) && ray.rdepth < max_refl;
+        const bool pt = mat_transparent(m) && ray.tdepth < max_transp && get_color<TEX>(lc, h).w != 1.0f;
         push_r = pr && sp < cap;
         push_t = pt && sp + int(push_r) < cap;
         if ((pr && !push_r) || (pt && !push_t)) flags |= VRT_HIT_FLAG_STACK_FULL;
@@ -649,11 +675,16 @@ __global__ void __launch_bounds__(kWgThreads, TREE ? kTreeWaves : (DEFER ? kDefe
 // Every deferred pixel is rendered exactly once, with the same exact path and epilogue as the
 // in-lane fallback, so images are identical. Workgroup 0 zeroes the other counter set for the
 // next launch on the stream (none of this launch's kernels reads it).
-// WAVES: resident waves per SIMD the instance is built for. 7 (72 VGPRs, ~1 KB of spills per lane)
-// for whole frames, where its waves share the CUs with the next frames' certified passes (fewer
-// cost 10-30 %, profiles/r03_s25; a spill-free 3-wave instance there: C3 0.0388 -> 0.049 ms per
-// frame at 8.7 instead of 17.4 MB of HBM writes, r06_s11); kFatWaves = 3 (no spills: shorter
-// exact walks; 168 VGPRs) for colour-only bands of under 4 dispatch rounds and synchronous frames,
+// WAVES: resident waves per SIMD the instance is built for (exact_pass_kernel; the whole-frame instances
+// run under a VGPR cap instead, exact_pass_kernel_capped below). Whole frames, whose exact waves share the
+// CUs with the next frames' certified passes, ran at 7 (72 VGPRs, ~1 KB of spills per lane) until r13:
+// fewer waves cost 10-30 % while the certified waves took 72 VGPRs themselves (profiles/r03_s25; a
+// spill-free 3-wave instance there: C3 0.0388 -> 0.049 ms per frame at 8.7 instead of 17.4 MB of HBM writes,
+// r06_s11). Against 56-VGPR certified waves, 8 to a SIMD, a 120-VGPR exact wave displaces one of them as
+// the 72-VGPR wave did, spills nothing and is the default for colour frames (kExactVgprs, vrt_tuning.h: C3
+// 0.0303 -> 0.0287 ms per frame, profiles/r13_exact/); textured frames keep kExactWaves = 7.
+// kFatWaves = 3 (no spills: shorter exact walks; 130-134 VGPRs) for colour-only bands of under 4
+// dispatch rounds and synchronous frames,
 // whose frame time is the certified pass plus this pass's latency (a.exact_fat: C4 k = 8 0.0229 ->
 // 0.0222, C3 k = 2 0.0275 -> 0.0267 ms at 4 waves, profiles/r03_s67; 3 waves, which no longer
 // spill where 4 now do: C4 synchronous frame 0.2125 -> 0.2059 ms, bands of C3/C4 k = 4, 8
@@ -662,19 +693,31 @@ __global__ void __launch_bounds__(kWgThreads, TREE ? kTreeWaves : (DEFER ? kDefe
 // whose frame time includes this pass's span: a sparse wave's span is its slowest walk, and a lone
 // wave's walks cost the same per step with 16 lanes as with 64 (C4 k = 8 band 0.0222 -> 0.0200 ms,
 // exact-pass span 58 -> 49 us; whole frames +1-3 %: more waves, profiles/r04_exact/)
-template <bool TEX, int CERT, int WAVES = kExactWaves, uint32_t SB = kSparseBatch, bool FB = false>
-__global__ void __launch_bounds__(64, WAVES) exact_pass_kernel(KArgs a, const uint16_t* __restrict__ vox,
-                                                                     float4* __restrict__ out) {
+//
+// The pass's body, shared by the kernels below. Its colour instances (LATE = !TEX) read the launch
+// late, as the certified pass does (late_kargs, vrt_cert.h): the Ctx comes without the sun, the sky
+// factor and the atlas (exact_pixel reads them after the primary walk and per bounce), and the frame's
+// outputs are read at the store. There the segment counters of the deferred list (8 sparse, 8 dense)
+// are summed once and read again per batch, through the same opaque view, where the batch's entry is
+// looked up: held in SGPRs from the kernel's start they were 16 scalar registers live across every
+// walk, spilled into VGPR lanes (v_writelane) that the walks then lacked. The textured instances
+// keep them in SGPRs: with the per-batch reads textured C3 and C4 ran 0.4-0.8 % slower than before
+// the change, with the counters kept 0.8 % faster (profiles/r13_exact/ab_bench.txt).
+template <bool TEX, int CERT, uint32_t SB, bool FB>
+__device__ __forceinline__ void exact_pass_body(const KArgs& a, const uint16_t* __restrict__ vox,
+                                                float4* __restrict__ out) {
+  constexpr bool LATE = !TEX;
   const uint32_t* ctr = a.defer;
   if (blockIdx.x == 0 && threadIdx.x < 2u * kOrdClasses) {  // both kinds of the other set, for the next launch
     const uint32_t l = threadIdx.x;
     a.defer[(((l / kOrdClasses) * 2u + (a.defer_e ^ 1u)) * kOrdClasses + l % kOrdClasses) * kOrdCtrStride] = 0u;
   }
+  // (ns, nd: dead in the LATE instances, which read the counters again per batch)
   uint32_t ns[kOrdClasses], nd[kOrdClasses], total_s = 0, total_d = 0;
 #pragma unroll
   for (uint32_t q = 0; q < kOrdClasses; ++q) {
-    // wave-uniform: kept in SGPRs (as VGPRs they were spilled to scratch by every workgroup,
-    // idle ones included, before the early exit below)
+    // (readfirstlane: wave-uniform values in SGPRs; as VGPRs the counts were spilled to scratch by every
+    // workgroup, idle ones included, before the early exit below)
     ns[q] = uint32_t(__builtin_amdgcn_readfirstlane(int(ctr[(a.defer_e * kOrdClasses + q) * kOrdCtrStride])));
     nd[q] = uint32_t(__builtin_amdgcn_readfirstlane(int(ctr[((2u + a.defer_e) * kOrdClasses + q) * kOrdCtrStride])));
     total_s += ns[q];
@@ -689,7 +732,7 @@ __global__ void __launch_bounds__(64, WAVES) exact_pass_kernel(KArgs a, const ui
   const uint32_t lane = lane_id();
   STAMP_PASS_BEGIN();
   Ctx c;
-  init_ctx(c, a, vox);
+  init_ctx<LATE>(c, a, vox);
   __shared__ float4 ax_tab[64 * 3];
   c.ax = &ax_tab[lane * kAxLane];
   for (uint32_t b = blockIdx.x; b < batches; b += gridDim.x) {
@@ -699,16 +742,33 @@ __global__ void __launch_bounds__(64, WAVES) exact_pass_kernel(KArgs a, const ui
     const bool dense = b < total_d;
     uint32_t idx = dense ? b : (b - total_d) * SB + lane;
     if (!dense && (lane >= SB || idx >= total_s)) continue;
-    uint32_t seg = 0;
+    // the entry's segment. LATE: this kind's counters read again (unchanged since the sums above: only
+    // the certified pass before this kernel wrote them), the list's base and segment size with them
+    uint32_t seg = 0, e;
+    if constexpr (LATE) {
+      LateKArgs* kq = late_kargs();
+      const uint32_t kind = uint32_t(__builtin_amdgcn_readfirstlane(dense ? 2 : 0));  // (b is wave-uniform)
+      const uint32_t* cq = kq->defer + (kind + kq->defer_e) * kOrdClasses * kOrdCtrStride;
 #pragma unroll
-    for (uint32_t q = 0; q + 1u < kOrdClasses; ++q) {
-      const uint32_t nq = dense ? nd[q] : ns[q];
-      const bool past = seg == q && idx >= nq;
-      idx -= past ? nq : 0u;
-      seg += past ? 1u : 0u;
+      for (uint32_t q = 0; q + 1u < kOrdClasses; ++q) {
+        const uint32_t nq = uint32_t(__builtin_amdgcn_readfirstlane(int(cq[q * kOrdCtrStride])));
+        const bool past = seg == q && idx >= nq;
+        idx -= past ? nq : 0u;
+        seg += past ? 1u : 0u;
+      }
+      const uint32_t* list = kq->defer + kDeferHdr + seg * kq->defer_seg;
+      e = dense ? list[kq->defer_seg - 64u * (idx + 1u) + lane] : list[idx];
+    } else {
+#pragma unroll
+      for (uint32_t q = 0; q + 1u < kOrdClasses; ++q) {
+        const uint32_t nq = dense ? nd[q] : ns[q];
+        const bool past = seg == q && idx >= nq;
+        idx -= past ? nq : 0u;
+        seg += past ? 1u : 0u;
+      }
+      const uint32_t* list = a.defer + kDeferHdr + seg * a.defer_seg;
+      e = dense ? list[a.defer_seg - 64u * (idx + 1u) + lane] : list[idx];
     }
-    const uint32_t* list = a.defer + kDeferHdr + seg * a.defer_seg;
-    const uint32_t e = dense ? list[a.defer_seg - 64u * (idx + 1u) + lane] : list[idx];
     if (e == ~0u) continue;  // a lane of a dense chunk whose pixel the certified pass settled
     Ray ray;
     if constexpr (FB) {
@@ -726,21 +786,66 @@ __global__ void __launch_bounds__(64, WAVES) exact_pass_kernel(KArgs a, const ui
     float hit_len = 0.0f;
     f3 color = mk(0.0f, 0.0f, 0.0f);
     __shared__ float lstk[kStackWords * 64];
-    (void)exact_pixel<false, TEX, CERT >= 1, CERT == 2 && !TEX, 64>(a, c, ray, color, k, steps, flags,
-                                                                    hit_vidx, hit_len, &lstk[lane]);
-    if constexpr (FB) {
-      // the pixel and its frame re-derived from e (only e stays live across the exact path)
-      uint32_t e2 = e;
-      asm volatile("" : "+v"(e2));  // not CSE'd with the decode above (whose results would stay live)
-      store_pixel(a, frame_view(a, e2 >> 29), out,
-                  size_t((e2 >> 16) & 0x1FFFu) * size_t(a.pitch) + size_t(e2 & 0xFFFFu), color);
+    (void)exact_pixel<false, TEX, CERT >= 1, CERT == 2 && !TEX, 64, LATE>(a, c, ray, color, k, steps, flags,
+                                                                          hit_vidx, hit_len, &lstk[lane]);
+    // the pixel and its frame re-derived from e (only e stays live across the exact path)
+    uint32_t e2 = e;
+    if constexpr (FB || LATE) asm volatile("" : "+v"(e2));  // not CSE'd with the decode above (whose results would stay live)
+    const uint32_t row = FB ? (e2 >> 16) & 0x1FFFu : e2 >> 16;
+    if constexpr (LATE) {
+      LateKArgs* ka = late_kargs();
+      uint32_t *cur = ka->cur, *raw = ka->raw;
+      if constexpr (FB) {
+        const uint32_t f = e2 >> 29;
+        if (f != 0u) {
+          cur = ka->fb[f - 1u].cur;
+          raw = ka->fb[f - 1u].raw;
+        }
+      }
+      store_pixel(*ka, FrameView{nullptr, 0.0f, cur, raw}, out, size_t(row) * size_t(ka->pitch) + size_t(e2 & 0xFFFFu),
+                  color);
     } else {
-      store_pixel(a, FrameView{a.inv_pv, a.time, a.cur, a.raw}, out,
-                  size_t(e >> 16) * size_t(a.pitch) + size_t(e & 0xFFFFu), color);
+      store_pixel(a, FB ? frame_view(a, e2 >> 29) : FrameView{a.inv_pv, a.time, a.cur, a.raw}, out,
+                  size_t(row) * size_t(a.pitch) + size_t(e2 & 0xFFFFu), color);
     }
     STAMP_PASS_BATCH(dense);
   }
   STAMP_PASS_END(lane);
+}
+
+// The kernel's first argument where it lies, in the kernarg segment (offset 0). The kernels below hand
+// their body this view: a reference to the by-value parameter made the frame-batch instances keep a
+// copy of all of KArgs in scratch (they index KArgs::fb by a lane's frame), 1.1 KB per lane.
+// This view, late_kargs and late_ctx (vrt_cert.h) all read offset 0: KArgs must stay the FIRST parameter
+// of every kernel that inlines exact_pass_body or exact_pixel<..., LATE> (the three kernels below), as it
+// is of the certified pass. The parameter itself is not read in them: it only lays the segment out.
+__device__ __forceinline__ const KArgs& kernel_kargs() {
+  return *(const KArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+}
+template <bool TEX, int CERT, int WAVES = kExactWaves, uint32_t SB = kSparseBatch, bool FB = false>
+__global__ void __launch_bounds__(64, WAVES) exact_pass_kernel(KArgs /* first: kernel_kargs() */,
+                                                               const uint16_t* __restrict__ vox,
+                                                               float4* __restrict__ out) {
+  exact_pass_body<TEX, CERT, SB, FB>(kernel_kargs(), vox, out);
+}
+// The colour whole-frame instances under a VGPR cap (kExactVgprs, vrt_tuning.h) instead of a whole
+// number of waves. amdgpu_num_vgpr takes an integer constant, no template argument: hence a kernel of
+// its own for the cap.
+template <int CERT, uint32_t SB, bool FB>
+__global__ void __launch_bounds__(64, exact_cap_waves(kExactVgprs))
+    __attribute__((amdgpu_num_vgpr(exact_cap_attr(kExactVgprs))))
+    exact_pass_kernel_capped(KArgs /* first: kernel_kargs() */, const uint16_t* __restrict__ vox,
+                             float4* __restrict__ out) {
+  exact_pass_body<false, CERT, SB, FB>(kernel_kargs(), vox, out);
+}
+using ExactPassFn = void (*)(KArgs, const uint16_t*, float4*);
+// the colour whole-frame instance of a launch: under the cap where one is set (CAP: kExactVgprs)
+template <int CAP>
+static ExactPassFn exact_pass_whole_frame(bool fb) {
+  if constexpr (CAP == 0)
+    return fb ? exact_pass_kernel<false, 2, kExactWaves, kSparseBatch, true> : exact_pass_kernel<false, 2>;
+  else
+    return fb ? exact_pass_kernel_capped<2, kSparseBatch, true> : exact_pass_kernel_capped<2, kSparseBatch, false>;
 }
 
 }  // namespace vrt
@@ -785,13 +890,11 @@ void launch_render(const KArgs& a, bool stats, const uint16_t* vox, float4* out,
               : a.tree   ? (fb ? render_kernel<false, false, 2, false, true, true, true>
                                : render_kernel<false, false, 2, false, true, false, true>)
                          : (fb ? render_kernel<false, false, 2, false, true, true> : render_kernel<false, false, 2, false, true>);
-    auto k2 = a.textured ? (fb ? exact_pass_kernel<true, 1, kExactWaves, kSparseBatchTex, true>
-                               : exact_pass_kernel<true, 1, kExactWaves, kSparseBatchTex>)
-                         : (a.exact_fat
-                                ? (fb ? exact_pass_kernel<false, 2, kFatWaves, kSparseBatchFat, true>
-                                      : exact_pass_kernel<false, 2, kFatWaves, kSparseBatchFat>)
-                                : (fb ? exact_pass_kernel<false, 2, kExactWaves, kSparseBatch, true>
-                                      : exact_pass_kernel<false, 2>));
+    ExactPassFn k2 = a.textured ? (fb ? exact_pass_kernel<true, 1, kExactWaves, kSparseBatchTex, true>
+                                      : exact_pass_kernel<true, 1, kExactWaves, kSparseBatchTex>)
+                     : a.exact_fat ? (fb ? exact_pass_kernel<false, 2, kFatWaves, kSparseBatchFat, true>
+                                         : exact_pass_kernel<false, 2, kFatWaves, kSparseBatchFat>)
+                                   : exact_pass_whole_frame<kExactVgprs>(fb);
     const uint32_t pad = a.tree ? 0u : kDeferLdsPad;  // (an occupancy A/B knob, vrt_tuning.h)
     if (ev_begin)
       hipExtLaunchKernelGGL(k1, g1, dim3(kWgThreads), pad, s, ev_begin, nullptr, 0, a, vox, out, hit, cnt_rep);

@@ -13,7 +13,7 @@
      defined(VRT_SPARSE_BATCH_FAT) || defined(VRT_EXACT_PRIO) || defined(VRT_FWD_CAP) || defined(VRT_WG_WAVES) || \
      defined(VRT_ORD_DIV) || defined(VRT_ORD_MIN_ROUNDS) || defined(VRT_DEFER_GRID_DIV) ||                      \
      defined(VRT_DEFER_GRID_DIV_COLOR) || defined(VRT_QUERY_WG_WAVES) || defined(VRT_TRACE_WG_WAVES) ||         \
-     defined(VRT_TRACE_MIN_WAVES) || defined(VRT_DEFER_LDS_PAD)) &&                                                                         \
+     defined(VRT_TRACE_MIN_WAVES) || defined(VRT_DEFER_LDS_PAD) || defined(VRT_EXACT_VGPRS)) &&                 \
     !defined(VRT_DIAGNOSTIC_BUILD)
 #error "the VRT_* tuning values are A/B knobs of make variant builds (make variant NAME=... DEFS=-DVRT_...=...)"
 #endif
@@ -32,6 +32,9 @@
 #endif
 #ifndef VRT_EXACT_WAVES
 #define VRT_EXACT_WAVES VRT_MIN_WAVES
+#endif
+#ifndef VRT_EXACT_VGPRS
+#define VRT_EXACT_VGPRS 120
 #endif
 #ifndef VRT_TREE_WAVES
 #define VRT_TREE_WAVES 5
@@ -109,6 +112,31 @@ constexpr int kDeferWaves = VRT_DEFER_WAVES;
 constexpr uint32_t kDeferLdsPad = VRT_DEFER_LDS_PAD;
 // resident waves per SIMD of the exact pass's whole-frame instance (see exact_pass_kernel, WAVES)
 constexpr int kExactWaves = VRT_EXACT_WAVES;
+// VGPR cap of the exact pass's colour whole-frame instances (exact_pass_kernel_capped): a budget between
+// the whole-wave steps kExactWaves can express (72, 80, 96, 128). 0: no cap, the instance is the kExactWaves
+// one. A capped instance promises 512 / cap waves per SIMD (the cap in 8-register granules) and carries
+// amdgpu_num_vgpr, which the compiler honours inside that promise (exact_cap_attr below).
+// 120: the smallest budget at which both instances spill no VGPR and their scratch is the bounce stack's
+// 544 B per lane (112: one spilled VGPR in the one-frame instance; 104: 4 and 7; 96: 10 and 12). A SIMD
+// full of certified waves holds 8 x 56 of its 512 VGPRs: the 72-VGPR exact wave already needed one of them
+// to leave, and with one gone 120 are free, so the wider wave displaces no more certified waves than the
+// narrow one did. C3 ms per frame, make variant builds and the parent alternating, three runs each
+// (profiles/r13_exact/screen.txt): parent 0.0303-0.0304; the restructured source at 72 VGPRs
+// 0.0294-0.0295; 96: 0.0290-0.0294; 112: 0.0288-0.0289; 120: 0.0286-0.0287; 128: 0.0287-0.0288; 160 (3
+// waves): 0.0286 / 0.0288 / 0.0306; a lone frame 0.1014-0.1036 -> 0.0885-0.0900 ms at 120. The product
+// library against the parent, alternating (profiles/r13_exact/ab_bench.txt): C3 0.0305 x 4 -> 0.0286-0.0288,
+// C1 0.1086-0.1088 -> 0.1068-0.1070, C2 0.0471-0.0474 -> 0.0466-0.0467, C4 0.1054 -> 0.1052-0.1057.
+// Textured whole frames keep the kExactWaves instance: under a cap of 120 it compiles to 1 spilled VGPR and
+// 560 B of scratch, under 96 to 33-35 spilled, and neither has been timed.
+constexpr int kExactVgprs = VRT_EXACT_VGPRS;
+static_assert(kExactVgprs == 0 || (kExactVgprs >= 64 && kExactVgprs <= 256 && kExactVgprs % 8 == 0),
+              "a VGPR cap of 64 to 256 in whole allocation granules, or 0 for none");
+// waves per SIMD a cap of v VGPRs allows (allocation granule: 8 registers of the SIMD's 512)
+constexpr int exact_cap_waves(int v) { return v > 0 ? 512 / ((v + 7) / 8 * 8) : 1; }
+// the attribute's argument for a cap of v registers: gfx90a and later share one file between VGPRs and
+// AGPRs, and the compiler takes the argument as half of it (it doubles the number; a value above the
+// promised waves' own budget it drops without a word: make asm shows the registers an instance got)
+constexpr int exact_cap_attr(int v) { return v > 0 ? v / 2 : 256; }
 // resident waves per SIMD of the certified pass with certified trees
 constexpr int kTreeWaves = VRT_TREE_WAVES;
 // resident waves per SIMD of the exact pass's short-band instance (see exact_pass_kernel, WAVES)
@@ -119,7 +147,10 @@ constexpr int kFatWaves = VRT_FAT_WAVES;
 // exact pass's span, which the frame's latency and a short run's drain wait for, at more waves: 32
 // with the column-block segments: the driver's 20-frame C3 command 0.0500 -> 0.0464 ms, latency
 // 0.123 -> 0.106 ms, 500 frames +0.8 % (C4 +-0, C2 +1 %); 16: 0.0485 / 0.103 / +2.6 %; 8: 0.0479 /
-// 0.102 / +6 % (profiles/r05_s10)
+// 0.102 / +6 % (profiles/r05_s10). Measured again on the 120-VGPR instance (r13, kExactVgprs): 16 against
+// 32, three alternating runs, C3 0.0293-0.0294 against 0.0286-0.0287 ms per frame (+2.3 %), a lone frame
+// 0.0796-0.0813 against 0.0885-0.0900 ms, the 20-frame command 0.0345-0.0349 against 0.0348-0.0358: 32 stays
+// (profiles/r13_exact/screen.txt)
 constexpr uint32_t kSparseBatch = VRT_SPARSE_BATCH;
 // the same for textured frames: 64 (many more sparse pixels, texel-edge hits: at 32 the extra waves
 // cost textured C3 0.0572 -> 0.0661 ms, C4 0.2329 -> 0.2894; profiles/r05_s30)
