@@ -26,8 +26,9 @@
  *     run on the context's first (root) device, as do the ray queries (vrt_cast_rays*,
  *     vrt_pick_pixels: which voxel a ray meets), the shaded ray queries (vrt_trace_rays*,
  *     vrt_trace_pixels: which colour a ray sees), the ID and depth pass (vrt_render_ids*: which
- *     voxel and face every pixel shows, and how far away) and the reprojected temporal filter
- *     (vrt_reproject_temporal_async, vrt_render_frame_reprojected: a history that follows the camera).
+ *     voxel and face every pixel shows, and how far away), the reprojected temporal filter
+ *     (vrt_reproject_temporal_async, vrt_render_frame_reprojected: a history that follows the camera)
+ *     and the ID-guided spatial filter (vrt_spatial_filter*: an estimate for a pixel without history).
  */
 #ifndef VRT_H
 #define VRT_H
@@ -617,6 +618,71 @@ int vrt_reproject_temporal_fetch_async(vrt_ctx* ctx, const vrt_camera* cam, cons
 /* The fetch mode of vrt_render_frame_reprojected's filter; VRT_FETCH_NEAREST in a new context. The history
  * (frames, IDs, matrix) is kept across a switch. An unknown mode is VRT_ERR_INVALID and changes nothing. */
 int vrt_set_reprojected_fetch(vrt_ctx* ctx, int32_t fetch);
+
+/* ---- ID-guided spatial filter (added within v15: detect by symbol lookup) --------------------- */
+/* The edge-aware filter the ID pass guides: an edge-stopping à-trous filter on RGBA8 frames whose edge stop
+ * is the ID record itself. A pixel that has just lost its history (a disoccluded pixel, an edited voxel, the
+ * first frame after a reset) shows its raw, noisy sample; this filter gives it the mean of its neighbours on
+ * the same surface. It follows the reprojected filter's rule: a tap counts only if it shows the same surface,
+ * words compared for equality, with no depth or normal threshold. All integer arithmetic
+ * (DESIGN.md §6 "Spatial filter"). */
+enum { VRT_GUIDE_FACE = 0, VRT_GUIDE_PLANE = 1 };
+
+/* One à-trous pass over rows [row0, row0 + rows) of a width x height frame: one kernel launch on hip_stream
+ * (one launch for vrt_set_launch_timing), on the context's first device: no memset, no allocation, no atomics,
+ * no context-owned state, capturable like vrt_render_ids_async.
+ * All buffers are DEVICE buffers indexed by the WHOLE frame: pixel (x, y) at [y * pitch + x]. d_in_rgba8 and
+ * d_out_rgba8 hold RGBA8 words, d_ids the frame's vrt_pixel_id records; d_keep and d_count (both optional)
+ * hold one byte per pixel and may have any alignment. The call writes rows [row0, row0 + rows) of d_out_rgba8
+ * and d_count and nothing else; it reads taps from the whole image, so d_out_rgba8 must not alias d_in_rgba8.
+ * Per pixel P = (x, y) of the band, in integers:
+ *   1. d_keep given and d_keep[P] != 0: out[P] = in[P], all four bytes, count[P] = 0. (A kept pixel still
+ *      serves as a tap of other pixels.)
+ *   2. tap (i, j), i, j in -2..2, sits at T = (x + i * step, y + j * step) with the weight K[i+2] * K[j+2],
+ *      K = {1, 4, 6, 4, 1};
+ *   3. T is valid iff it lies in [0, width) x [0, height), key(T) == key(P), and |dR| + |dG| + |dB| <= range
+ *      between in[T] and in[P] (the A bytes are ignored). A tap outside the image is never loaded, neither its
+ *      ID nor its colour. The centre is always valid;
+ *   4. key, VRT_GUIDE_FACE: both words of the record. (The ID pass writes every miss as {-1, 0}: all misses
+ *      share one key.)
+ *      key, VRT_GUIDE_PLANE: the face word, and for a hit (voxel_index >= 0) the cell coordinate along the
+ *      face's axis, (voxel_index >> ((face & 3) * log2 N)) & (N - 1) with N the resident volume's edge, in
+ *      place of the voxel index; a miss keeps its negative word. Coplanar faces of one material and one
+ *      orientation filter together. PLANE is meant for opaque surfaces: glass shows view-dependent content
+ *      across a plane;
+ *   5. wsum = the sum of the valid weights (36..256), acc_c = the sum of weight * byte_c over the valid taps;
+ *      out_c = (2 * acc_c + wsum) / (2 * wsum), integer floor, for c = R, G, B; A = 255;
+ *      count[P] = the number of valid taps, 1..25.
+ * VRT_ERR_NO_VOLUME without a resident volume (both guides). VRT_ERR_INVALID for a null d_in_rgba8, d_ids or
+ * d_out_rgba8, a bad image size (vrt_render_ids_async's rule), pitch < width, rows < 0 or a band outside the
+ * image, step outside 1..64, an unknown guide, range < 0 (765 or more disables the colour test),
+ * d_out_rgba8 == d_in_rgba8, d_ids not 8-byte or a colour buffer not 4-byte aligned. rows == 0 is a successful
+ * no-op. A failed call writes nothing. */
+int vrt_spatial_filter_async(vrt_ctx* ctx, int32_t width, int32_t height, int32_t pitch, int32_t step,
+                             int32_t guide, int32_t range, int32_t row0, int32_t rows,
+                             const uint32_t* d_in_rgba8, const vrt_pixel_id* d_ids, const uint8_t* d_keep,
+                             uint32_t* d_out_rgba8, uint8_t* d_count, void* hip_stream);
+
+/* `passes` passes (1..5) over HOST buffers of packed width x height, pass p = 0, 1, ... at step 2^p, each the
+ * pass above over the whole frame with the same ids, keep (optional), guide and range; synchronous, through
+ * context-owned device staging that grows on demand and is freed by vrt_destroy, on the main context stream
+ * of the first device. Errors as above; also VRT_ERR_INVALID for passes outside 1..5. */
+int vrt_spatial_filter(vrt_ctx* ctx, int32_t width, int32_t height, int32_t passes, int32_t guide, int32_t range,
+                       const uint8_t* rgba8, const vrt_pixel_id* ids, const uint8_t* keep, uint8_t* out_rgba8);
+
+/* The spatial passes of vrt_render_frame_reprojected; VRT_SPATIAL_OFF in a new context (the loop then runs
+ * exactly the launches described there). The passes run after the temporal filter, pass p at step 2^p, on the
+ * frame's noise-free IDs.
+ *   VRT_SPATIAL_DISPLAY: the returned frame is the passes applied to the temporal filter's output, without a
+ *     keep mask; the history stays the unfiltered temporal output, so the history chain is that of a context
+ *     with the passes off.
+ *   VRT_SPATIAL_FILL: the passes run with d_keep = the temporal filter's tap byte (the loop launches the fetch
+ *     with a tap buffer): a pixel with accepted history is kept, a pixel without gets its spatial estimate.
+ *     The filled frame is the returned frame and the next call's history.
+ * stats->kernel_ms spans to the last pass's end. The history (frames, IDs, matrix) is kept across a switch.
+ * An unknown mode or guide, passes outside 1..5 or range < 0 is VRT_ERR_INVALID and changes nothing. */
+enum { VRT_SPATIAL_OFF = 0, VRT_SPATIAL_DISPLAY = 1, VRT_SPATIAL_FILL = 2 };
+int vrt_set_reprojected_spatial(vrt_ctx* ctx, int32_t mode, int32_t passes, int32_t guide, int32_t range);
 
 /* ---- textured mode (voxel.glsl without _COLOR_ONLY) --------------------- */
 /* With vrt_params.color_only = 0 the kernel shades with the textured material table

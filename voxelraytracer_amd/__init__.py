@@ -17,6 +17,8 @@ from .abi import (  # noqa: F401  (re-exported vocabulary)
     COUNTER_NAMES,
     FETCH_BILINEAR,
     FETCH_NEAREST,
+    GUIDE_FACE,
+    GUIDE_PLANE,
     HIT_DTYPE,
     PIXEL_ID_DTYPE,
     RAY_COLOR_DTYPE,
@@ -26,6 +28,9 @@ from .abi import (  # noqa: F401  (re-exported vocabulary)
     SCENE_REFRACTION,
     SCENE_TERRAIN,
     SCENES,
+    SPATIAL_DISPLAY,
+    SPATIAL_FILL,
+    SPATIAL_OFF,
     Camera,
     Params,
     PixelId,
@@ -529,6 +534,41 @@ class Renderer:
     def reprojected_history_reset(self):
         """vrt_reprojected_history_reset: the next render_frame_reprojected has no history."""
         self._check(self._lib.vrt_reprojected_history_reset(self._h), "vrt_reprojected_history_reset")
+
+    def spatial_filter_async(self, width: int, height: int, pitch: int, step: int, guide: int, range: int, row0: int,
+                             rows: int, d_in: int, d_ids: int, d_keep: int, d_out: int, d_count: int = 0,
+                             stream: int = 0):
+        """vrt_spatial_filter_async: one ID-guided à-trous pass at `step` over rows [row0, row0 + rows) of a
+        width x height frame, one kernel launch enqueued on a HIP stream. Device pointers, all indexed by the
+        whole frame with `pitch` pixels per row: d_in and d_out RGBA8 words (they must differ), d_ids the
+        frame's 8-byte ID records, d_keep (0: none) one byte per pixel, non-zero for a pixel that is copied
+        through, d_count (0: none) one byte per pixel, the number of valid taps. guide: GUIDE_FACE or
+        GUIDE_PLANE; range: the largest |dR| + |dG| + |dB| of a valid tap (765: no colour test)."""
+        self._check(self._lib.vrt_spatial_filter_async(
+            self._h, width, height, pitch, step, guide, range, row0, rows, d_in or None, d_ids or None,
+            d_keep or None, d_out or None, d_count or None, stream or None), "vrt_spatial_filter_async")
+
+    def spatial_filter(self, rgba8, ids, passes: int = 3, guide: int = GUIDE_FACE, range: int = 765, keep=None):
+        """vrt_spatial_filter: `passes` passes (pass p at step 2^p) over the host frame rgba8[H, W, 4] uint8
+        with the ID records ids[H, W] (PIXEL_ID_DTYPE, e.g. render_ids') and an optional keep[H, W] uint8
+        (non-zero: the pixel is copied through). Returns the filtered frame [H, W, 4] uint8."""
+        src = np.ascontiguousarray(rgba8, dtype=np.uint8)
+        h, w = src.shape[:2]
+        rec = np.ascontiguousarray(ids, dtype=PIXEL_ID_DTYPE).reshape(h, w)
+        kp = None if keep is None else np.ascontiguousarray(keep, dtype=np.uint8).reshape(h, w)
+        out = np.empty((h, w, 4), dtype=np.uint8)
+        self._check(self._lib.vrt_spatial_filter(self._h, w, h, passes, guide, range, src.ctypes.data, rec.ctypes.data,
+                                                 None if kp is None else kp.ctypes.data, out.ctypes.data),
+                    "vrt_spatial_filter")
+        return out
+
+    def set_reprojected_spatial(self, mode: int, passes: int = 3, guide: int = GUIDE_FACE, range: int = 765):
+        """vrt_set_reprojected_spatial: the spatial passes of render_frame_reprojected. SPATIAL_OFF (the default),
+        SPATIAL_DISPLAY (the returned frame is filtered, the history is not) or SPATIAL_FILL (pixels without
+        accepted history get their spatial estimate, in the returned frame and in the history). The history is
+        kept across a switch."""
+        self._check(self._lib.vrt_set_reprojected_spatial(self._h, mode, passes, guide, range),
+                    "vrt_set_reprojected_spatial")
 
     def debug_packed_volume(self) -> np.ndarray:
         """The kernel's device volumes [octant][z][y][x] ((N+1)^3 u16 voxel | G << 8 each; 8

@@ -152,6 +152,13 @@ PIXEL_ID_DTYPE = [("voxel_index", "<i4"), ("face", "<u4")]
 FETCH_NEAREST = 0
 FETCH_BILINEAR = 1
 
+# ID-guided spatial filter (vrt_spatial_filter*): the guide's key, and the loop's modes (vrt_set_reprojected_spatial)
+GUIDE_FACE = 0
+GUIDE_PLANE = 1
+SPATIAL_OFF = 0
+SPATIAL_DISPLAY = 1
+SPATIAL_FILL = 2
+
 # name -> (restype, argtypes): every function include/vrt.h declares
 # entry points added after ABI v12 (an older build loaded by VRT_LIB with VRT_LIB_ABI=<its version>
 # may lack exactly these)
@@ -168,7 +175,9 @@ ADDED_IN = {"vrt_render_temporal_batch_async": 14, "vrt_set_cert_trees": 15,
             "vrt_camera_forward": 16, "vrt_reproject_temporal_async": 16, "vrt_render_frame_reprojected": 16,
             "vrt_reprojected_history_reset": 16,
             # added within v15 after the reprojected filter (bilinear history fetch)
-            "vrt_reproject_temporal_fetch_async": 16, "vrt_set_reprojected_fetch": 16}
+            "vrt_reproject_temporal_fetch_async": 16, "vrt_set_reprojected_fetch": 16,
+            # added within v15 after the bilinear fetch (ID-guided spatial filter)
+            "vrt_spatial_filter_async": 16, "vrt_spatial_filter": 16, "vrt_set_reprojected_spatial": 16}
 
 SIGNATURES = {
     "vrt_abi_version": (C.c_int, []),
@@ -233,6 +242,13 @@ SIGNATURES = {
                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                      C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vrt_set_reprojected_fetch": (C.c_int, [C.c_void_p, C.c_int32]),
+    # added within v15 (detect by symbol lookup): ID-guided spatial filter
+    "vrt_spatial_filter_async": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                           C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vrt_spatial_filter": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vrt_set_reprojected_spatial": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "vrt_build_scene_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p]),
     "vrt_debug_packed_volume": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
     "vrt_debug_collectives": (C.c_int, [C.c_void_p]),

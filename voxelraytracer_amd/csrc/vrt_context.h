@@ -221,6 +221,15 @@ struct vrt_ctx {
   int32_t rp_fetch = VRT_FETCH_NEAREST;  // vrt_set_reprojected_fetch: which filter the loop launches
   float rp_pv[16] = {};
   hipEvent_t ev_rp_beg = nullptr, ev_rp_end = nullptr;
+  // vrt_set_reprojected_spatial: the loop's spatial passes (off in a new context), and their staging, allocated
+  // with the first frame that runs them: two frames the passes ping-pong through and the filter's tap bytes
+  int32_t rp_spatial = VRT_SPATIAL_OFF, rp_sp_passes = 3, rp_sp_guide = VRT_GUIDE_FACE, rp_sp_range = 765;
+  vrt::Stage<uint32_t> d_rp_sp[2];
+  vrt::Stage<uint8_t> d_rp_taps;
+  // first device: staging of the synchronous vrt_spatial_filter: two frames, the IDs and the keep bytes
+  vrt::Stage<uint32_t> d_sp_rgba[2];
+  vrt::Stage<vrt_pixel_id> d_sp_ids;
+  vrt::Stage<uint8_t> d_sp_keep;
   // ABI v12: this process's rank of a one-process-per-GPU job (vrt_comm_join): one RCCL
   // communicator per lane, so that frames in flight on different lane streams gather without
   // ordering each other (a communicator's operations run in issue order)

@@ -190,6 +190,26 @@ void launch_reproject(const KArgs& a, const ReprojArgs& r, hipStream_t s, hipEve
 // reproject_bilinear_kernel. One launch either way; fetch is one of the two modes (the caller checks)
 void launch_reproject_fetch(const KArgs& a, const ReprojArgs& r, int32_t fetch, uint8_t* taps, hipStream_t s,
                             hipEvent_t ev_begin = nullptr, hipEvent_t ev_end = nullptr);
+// spatial_direct_kernel / spatial_lds_kernel (vrt_spatial_kernels.h): one à-trous pass over rows [row0, row0 +
+// rows) of a width x height frame; every buffer whole-frame indexed, pixel (x, y) at [y * pitch + x]. keep and
+// count may be null. nlog: log2 of the resident volume's edge (the PLANE guide's key). One launch, a 16x16 tile
+// per workgroup of kSpatialWg threads; the form is chosen per step (kSpatialLdsSteps, vrt_tuning.h).
+// ev_begin / ev_end: optional device timestamps
+struct SpatialArgs {
+  int32_t width, height, pitch, step, guide, range, row0, rows;
+  uint32_t nlog;
+  const uint32_t* in;
+  const uint2* ids;
+  const uint8_t* keep;
+  uint32_t* out;
+  uint8_t* count;
+};
+constexpr int kSpatialWg = 256;
+// whether a pass at `step` launches the LDS-staged form
+constexpr bool spatial_lds_form(int32_t step) {
+  return (step == 1 || step == 2 || step == 4) && ((kSpatialLdsSteps >> step) & 1u) != 0;
+}
+void launch_spatial(const SpatialArgs& a, hipStream_t s, hipEvent_t ev_begin = nullptr, hipEvent_t ev_end = nullptr);
 // fold the counter replicas into dst (accumulating) and re-zero them
 void launch_reduce_counters(unsigned long long* rep, unsigned long long* dst, hipStream_t s);
 // in-place edit of the box [lo, lo + ext) (vrt_update_volume_region), inside [0, N)^3:

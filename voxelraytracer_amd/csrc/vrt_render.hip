@@ -4,7 +4,8 @@
 // frame kernels and the host launch wrappers; the rest is in the headers included below, in
 // dependency order (vrt_tuning.h through vrt_internal.h), and in vrt_query_kernels.h,
 // vrt_trace_kernels.h, vrt_ids_kernels.h and vrt_reproject_kernels.h (the ray-query, shaded ray-query,
-// ID-pass and reprojected-filter kernels, included after the primary ray and exact_pixel they call).
+// ID-pass and reprojected-filter kernels, included after the primary ray and exact_pixel they call),
+// and in vrt_spatial_kernels.h (the ID-guided spatial filter, which calls none of them).
 //
 // One work-item per pixel; a 128-thread workgroup covers a 16x8 pixel tile and each wave64 an
 // 8x8 sub-tile, so the 64 rays of a wave start coherent. Every float operation of the DDA is
@@ -858,6 +859,8 @@ static ExactPassFn exact_pass_whole_frame(bool fb) {
 #include "vrt_ids_kernels.h"
 // the reprojected temporal filter (vrt_reproject_temporal_async): after temporal_blend and primary_ray
 #include "vrt_reproject_kernels.h"
+// the ID-guided spatial filter (vrt_spatial_filter_async): it calls nothing of the kernels above
+#include "vrt_spatial_kernels.h"
 
 namespace vrt {
 
@@ -983,6 +986,18 @@ void launch_reproject_fetch(const KArgs& a, const ReprojArgs& r, int32_t fetch, 
     hipExtLaunchKernelGGL(kern, grid, dim3(kReprojWg), 0, s, ev_begin, ev_end, 0, a, r, taps);
   else
     hipLaunchKernelGGL(kern, grid, dim3(kReprojWg), 0, s, a, r, taps);
+}
+
+void launch_spatial(const SpatialArgs& a, hipStream_t s, hipEvent_t ev_begin, hipEvent_t ev_end) {
+  auto kern = !spatial_lds_form(a.step) ? spatial_direct_kernel
+              : a.step == 1             ? spatial_lds_kernel<1>
+              : a.step == 2             ? spatial_lds_kernel<2>
+                                        : spatial_lds_kernel<4>;
+  const dim3 grid(uint32_t(a.width + 15) / 16u, uint32_t(a.rows + 15) / 16u);
+  if (ev_begin || ev_end)
+    hipExtLaunchKernelGGL(kern, grid, dim3(kSpatialWg), 0, s, ev_begin, ev_end, 0, a);
+  else
+    hipLaunchKernelGGL(kern, grid, dim3(kSpatialWg), 0, s, a);
 }
 
 void launch_reduce_counters(unsigned long long* rep, unsigned long long* dst, hipStream_t s) {

@@ -13,7 +13,8 @@
      defined(VRT_SPARSE_BATCH_FAT) || defined(VRT_EXACT_PRIO) || defined(VRT_FWD_CAP) || defined(VRT_WG_WAVES) || \
      defined(VRT_ORD_DIV) || defined(VRT_ORD_MIN_ROUNDS) || defined(VRT_DEFER_GRID_DIV) ||                      \
      defined(VRT_DEFER_GRID_DIV_COLOR) || defined(VRT_QUERY_WG_WAVES) || defined(VRT_TRACE_WG_WAVES) ||         \
-     defined(VRT_TRACE_MIN_WAVES) || defined(VRT_DEFER_LDS_PAD) || defined(VRT_EXACT_VGPRS)) &&                 \
+     defined(VRT_TRACE_MIN_WAVES) || defined(VRT_DEFER_LDS_PAD) || defined(VRT_EXACT_VGPRS) ||                  \
+     defined(VRT_SPATIAL_LDS_STEPS)) &&                                                                        \
     !defined(VRT_DIAGNOSTIC_BUILD)
 #error "the VRT_* tuning values are A/B knobs of make variant builds (make variant NAME=... DEFS=-DVRT_...=...)"
 #endif
@@ -77,6 +78,9 @@
 #endif
 #ifndef VRT_TRACE_MIN_WAVES
 #define VRT_TRACE_MIN_WAVES 6
+#endif
+#ifndef VRT_SPATIAL_LDS_STEPS
+#define VRT_SPATIAL_LDS_STEPS 0x16
 #endif
 
 namespace vrt {
@@ -196,6 +200,15 @@ static_assert(kTraceWgWaves >= 1 && kTraceWgWaves <= 4, "1 to 4 waves per trace 
 // 2 M scattered rays 5.90 -> 5.47 and 5.75 -> 5.36 ms; 7 (72 VGPRs, 1-21 spilled) is no faster: 0.2505,
 // 0.3678, 5.45, 5.32 (profiles/ray_trace_ab.txt; the frame's STATS instance runs at 7 with 24-40 spilled)
 constexpr int kTraceMinWaves = VRT_TRACE_MIN_WAVES;
+
+// the steps at which a spatial-filter pass (vrt_spatial_kernels.h) launches its LDS-staged form, bit `step` for
+// step 1, 2 and 4 (the steps that have one); every other step, and a cleared bit, launch the direct gather.
+// 0x16: staged at all three. One pass over 1920x1080 at C3, FACE guide, no count buffer, the product library
+// against a VRT_SPATIAL_LDS_STEPS=0 build (each three runs of 21 launches in a process of its own, ms staged ->
+// direct): step 1 0.0246 -> 0.0482, step 2 0.0259 -> 0.0479, step 4 0.0294 -> 0.0472; the direct gather at step 8
+// 0.0468 and 0.0469 in the two processes, at step 16 0.0528 and 0.0527 (profiles/spatial_bench.txt)
+constexpr uint32_t kSpatialLdsSteps = VRT_SPATIAL_LDS_STEPS;
+static_assert((kSpatialLdsSteps & ~0x16u) == 0, "only steps 1, 2 and 4 have an LDS-staged form");
 
 }  // namespace vrt
 
