@@ -116,6 +116,14 @@ struct CertStartK {
   int mx, my, mz;
   float b0, U2;
 };
+// CertShadowK (the shadow walk of a primary hit, cert_shade_hit<.., KAX>): the first planes sig_b = (float(c_b +
+// u_b) - X_b) rcp_b as cert_start_sun formed them for its lead test: the walk's own expression on the walk's
+// own operands (the shadow origin X, the start cell, sun_rcp, u_b = sun_step[b] > 0), so the walk takes the
+// values instead of twelve more instructions: they are the walk's own bit for bit, and nothing it assumes
+// about its start changes.
+struct CertShadowK {
+  f3 sig;
+};
 // The launch's arguments read again where the certified pass (LEAN) first needs them, after the
 // primary walk: KArgs is the kernels' first argument, at offset 0 of the kernarg segment, and the
 // pointer is kept opaque so that the scalar loads through it are not hoisted back above the walk. The
@@ -130,8 +138,8 @@ __device__ __forceinline__ LateKArgs* late_kargs() {
 }
 // The shadow walk's functions of the sun alone are such arguments (KArgs::sun_*, formed once per launch
 // on the host, sun_consts in vrt_context.cpp: IEEE single operations in the kernel's order, no
-// contraction): a LateKArgs pointer handed to cert_shade_hit<.., KAX> and on to its cert_walk stands for
-// "read them from the launch". sun_ok is fast_path_ok(sun_n); the other fields mean something only then.
+// contraction): cert_shade_hit<.., KAX> reads them through a LateKArgs pointer and hands it on to its
+// cert_walk<.., KSUN>. sun_ok is fast_path_ok(sun_n); the other fields mean something only then.
 
 // Certified walk from P along D (every |d| in the fast-path range) with rcp ~ 1/D (a few ulp
 // suffice: the walk's own rounding is inside the 4e-5 allowance of the bound), starting in cell
@@ -177,12 +185,16 @@ __device__ __forceinline__ LateKArgs* late_kargs() {
 //    s1: `uj > s1` is false, as the test `G >= 2` decided before. An infinite or NaN A or B (never
 //    at fast-path directions) fails the compare too: no jump.
 // The two lattice cameras of DESIGN.md §10 (certified trees) are not touched by this.
-template <bool SHADOW, bool LEAN = false, bool ED = true>
+// KSUN (LEAN): the direction is the sun and sk holds its launch constants (sh0: the caller's first planes too).
+// A template flag, not a test of sk: the late pointer is opaque (late_kargs), so `sk != nullptr` was decided
+// by every wave, in scalar branches around each constant and nine per-lane selects of wave-uniform values.
+template <bool SHADOW, bool LEAN = false, bool ED = true, bool KSUN = false>
 __device__ __forceinline__ CertResult cert_walk(const Ctx& c, const f3 P, const f3 D, const f3 rcp, const float U,
                                 int cx, int cy, int cz, const float e0, const f3 ed,
                                 const float len0b, const uint32_t medium, const uint32_t tex0 = ~0u,
                                 const CertStartK* __restrict__ st0 = nullptr,
-                                LateKArgs* sk = nullptr) {
+                                LateKArgs* sk = nullptr, const CertShadowK* __restrict__ sh0 = nullptr) {
+  static_assert(!KSUN || (LEAN && SHADOW), "the sun's launch constants: the certified pass's shadow walks");
   CertResult r;
   r.res = CERT_UNSURE;
   r.byte = 0u;
@@ -192,8 +204,9 @@ __device__ __forceinline__ CertResult cert_walk(const Ctx& c, const f3 P, const 
   r.eu = 0.0f;
   r.us = 0.0f;
   // (sk: the shadow walk's direction is the sun: its signs, octant and |S|_1 are launch constants)
-  const bool ksun = LEAN && sk != nullptr;
+  constexpr bool ksun = KSUN;
   const bool kst = LEAN && st0 != nullptr;  // (st0: the primary walk's start and launch constants, CertStartK)
+  const bool ksh = KSUN && sh0 != nullptr;  // (sh0: the shadow walk's first planes, CertShadowK)
   const int sx = ksun ? sk->sun_step[0] : (D.x > 0.0f ? 1 : -1), sy = ksun ? sk->sun_step[1] : (D.y > 0.0f ? 1 : -1),
             sz = ksun ? sk->sun_step[2] : (D.z > 0.0f ? 1 : -1);
   const int ux = ksun ? (sk->sun_step[0] > 0 ? 1 : 0) : (D.x > 0.0f ? 1 : 0), uy = ksun ? (sk->sun_step[1] > 0 ? 1 : 0) : (D.y > 0.0f ? 1 : 0),
@@ -227,8 +240,10 @@ __device__ __forceinline__ CertResult cert_walk(const Ctx& c, const f3 P, const 
   const f3 Da = mk(__builtin_fabsf(D.x), __builtin_fabsf(D.y), __builtin_fabsf(D.z));
   const int mx = kst ? st0->mx : ux - 1, my = kst ? st0->my : uy - 1, mz = kst ? st0->mz : uz - 1;
   // (st0: the first planes from the start's floored floats, the landing form below: CertStartK)
-  f3 sig = kst ? mk((st0->fl1.x - Ps.x) * ar.x, (st0->fl1.y - Ps.y) * ar.y, (st0->fl1.z - Ps.z) * ar.z)
-               : mk((float(cx + ux) - P.x) * rcp.x, (float(cy + uy) - P.y) * rcp.y, (float(cz + uz) - P.z) * rcp.z);
+  // (sh0: the caller's start formed the expression below already, CertShadowK)
+  f3 sig = kst   ? mk((st0->fl1.x - Ps.x) * ar.x, (st0->fl1.y - Ps.y) * ar.y, (st0->fl1.z - Ps.z) * ar.z)
+           : ksh ? sh0->sig
+                 : mk((float(cx + ux) - P.x) * rcp.x, (float(cy + uy) - P.y) * rcp.y, (float(cz + uz) - P.z) * rcp.z);
   // start: the unguarded box from the diagonal neighbour (G(v + s) + 1 in the guarded formula)
   // (tex0: that texel, loaded by the caller beside an earlier load; ~0u: load it here)
   uint32_t tex = (tex0 != ~0u ? tex0
@@ -514,6 +529,30 @@ __device__ __forceinline__ bool cert_start(const f3 X, const f3 D0, const f3 Dn,
   return okx && oky && okz;
 }
 
+// cert_start for the shadow ray of a primary hit (cert_shade_hit<.., KAX>; the new direction is the sun, sk its
+// launch constants): the same predicate and the same ed, with
+//  - d0a, the parent direction's face component, from the caller (the lit term selected it already);
+//  - the first planes kept for the walk (sh.sig: CertShadowK), u_b spelled as the walk spells it, sun_step[b]
+//    > 0, which is S_b > 0 (sun_consts): cert_start's w_b, same operations, same operands;
+//  - the face axis' exclusion and the conjunctions as integer | and &: the same truth table (each operand a
+//    comparison without side effects; tests/test_shadow_start_forms.py), without three branch regions.
+__device__ __forceinline__ bool cert_start_sun(const f3 X, const f3 D0, const float d0a, LateKArgs* sk, const f3 rcpn,
+                                               int fa, float e, int cx, int cy, int cz, f3& ed, CertShadowK& sh) {
+  ed = mk(2.0f * e * __builtin_fabsf(D0.x * rcpn.x), 2.0f * e * __builtin_fabsf(D0.y * rcpn.y),
+          2.0f * e * __builtin_fabsf(D0.z * rcpn.z));
+  const float rna = fa == 0 ? rcpn.x : (fa == 1 ? rcpn.y : rcpn.z);
+  const float lead = (e * __builtin_fabsf(d0a) + 1e-5f) * __builtin_fabsf(rna);
+  const int ux = sk->sun_step[0] > 0 ? 1 : 0, uy = sk->sun_step[1] > 0 ? 1 : 0, uz = sk->sun_step[2] > 0 ? 1 : 0;
+  sh.sig = mk((float(cx + ux) - X.x) * rcpn.x, (float(cy + uy) - X.y) * rcpn.y, (float(cz + uz) - X.z) * rcpn.z);
+  const f3 fr = mk(X.x - __builtin_floorf(X.x), X.y - __builtin_floorf(X.y), X.z - __builtin_floorf(X.z));
+  const f3 dm = mk(e * __builtin_fabsf(D0.x) + 2e-5f, e * __builtin_fabsf(D0.y) + 2e-5f,
+                   e * __builtin_fabsf(D0.z) + 2e-5f);
+  const int okx = int(fa == 0) | (int(sh.sig.x >= lead + ed.x + 1e-4f) & int(fr.x >= dm.x) & int(1.0f - fr.x >= dm.x));
+  const int oky = int(fa == 1) | (int(sh.sig.y >= lead + ed.y + 1e-4f) & int(fr.y >= dm.y) & int(1.0f - fr.y >= dm.y));
+  const int okz = int(fa == 2) | (int(sh.sig.z >= lead + ed.z + 1e-4f) & int(fr.z >= dm.z) & int(1.0f - fr.z >= dm.z));
+  return (okx & oky & okz) != 0;
+}
+
 // The cell before a hit cell along D on its crossed axis
 __device__ __forceinline__ void cell_before(const CertResult& h, const f3 D, int& x, int& y, int& z) {
   x = h.cx - (h.axis == 0 ? (D.x > 0.0f ? 1 : -1) : 0);
@@ -536,6 +575,30 @@ __device__ __forceinline__ Hit cert_hit_record(const Ray& ray, const CertResult&
   return hh;
 }
 
+// The face's normal -sign(D_a) e_a alone, as cert_hit_record forms it
+__device__ __forceinline__ f3 cert_hit_normal(const f3 D, int axis) {
+  f3 n = mk(0.0f, 0.0f, 0.0f);
+  set_comp(n, axis, -gsign(comp(D, axis)));
+  return n;
+}
+// cert_hit_record for a primary hit of the certified pass (LEAN: ray is the launch's primary ray, len 0):
+//  - len = h.u: cert_hit_record's 0.0f + h.u is h.u bit for bit unless h.u is -0, and the primary walk's
+//    planes are products of a positive difference (fl_b + 1 > Ps_b, CertStartK; a crossing's next plane lies
+//    ahead of it) and |1/d_b| > 0: h.u, their minimum, is never negative, -0 included;
+//  - the normal stays zero: cert_shade_hit<.., KAX> and cert_texel do not read it, and the generic lit term
+//    behind sun_ok == 0 forms it there (cert_hit_normal). It was formed for every hit before that branch.
+__device__ __forceinline__ Hit cert_hit_record_primary(const Ray& ray, const CertResult& h) {
+  Hit hh;
+  hh.found = true;
+  hh.voxel = h.byte;
+  hh.axis = h.axis;
+  hh.vidx = -1;
+  hh.len = h.u;
+  hh.point = mk(ray.pos.x + h.u * ray.dir.x, ray.pos.y + h.u * ray.dir.y, ray.pos.z + h.u * ray.dir.z);
+  hh.normal = mk(0.0f, 0.0f, 0.0f);
+  return hh;
+}
+
 // TraceWithShadow's colour update (voxel.glsl:395-418) for a certified hit of `ray`: the shadow
 // bit by a certified shadow walk from the hit, unless it cannot change the brightness (lit ==
 // ambient). false: unsure (colour untouched).
@@ -554,7 +617,26 @@ __device__ __forceinline__ bool cert_shade_hit(const Ctx& c, const Ray& ray, con
   //    p_a = (-S_a) D_a = -(S_a D_a) (negation commutes with rounding): the same products, the same order.
   // With a zero in S the zeros' signs can differ (-0 - -0 = +0: tests/test_cert_start_lit_forms.py finds
   // such suns), so the generic form stays behind the wave-uniform branch; it defers every lit hit there.
-  float lit, ns = 0.0f;
+  // (KAX: hh is cert_hit_record_primary's, its normal zero; the generic lit term forms the normal where it runs,
+  // from an opaque copy of the axis so that it is not merged back in front of the branch)
+  // KAX: the material is stone or grass. h is a certified hit of a primary walk in air, so its byte is an event
+  // of the air medium: the loop stops with CERT_HIT only where `ev` holds, cert_event<false>(b, 0), b != 0, and b
+  // is the byte it hands back; and cert_pixel has taken the glass hits (mat_id(b) == 2, b == 2) before it shades.
+  // The material tables' arms for air and glass (mat_kd, mat_ks, mat_exp, mat_color, shadow_free_hit) are
+  // selects on tests whose outcome this decides.
+  if constexpr (KAX) __builtin_assume(h.byte != 0u && h.byte != 2u);
+  float lit, ns = 0.0f, da = 0.0f;  // da (KAX, sun_ok): D_a, for the shadow's start too (cert_start_sun)
+  auto lit_generic = [&]() {
+    if constexpr (KAX) {
+      int ga = h.axis;
+      asm volatile("" : "+v"(ga));
+      Hit hg = hh;
+      hg.normal = cert_hit_normal(ray.dir, ga);
+      return lit_brightness<TEX>(hg, S, ray.dir);
+    } else {
+      return lit_brightness<TEX>(hh, S, ray.dir);
+    }
+  };
   if constexpr (KAX) {
     if (sk->sun_ok != 0u) {
       const int a = h.axis;
@@ -562,7 +644,8 @@ __device__ __forceinline__ bool cert_shade_hit(const Ctx& c, const Ray& ray, con
       // select of its fields became a load at a selected address and kept the ray in scratch, 48 B)
       f3 D = ray.dir;
       asm volatile("" : "+v"(D.x), "+v"(D.y), "+v"(D.z));
-      const float sa = a == 0 ? S.x : (a == 1 ? S.y : S.z), da = a == 0 ? D.x : (a == 1 ? D.y : D.z);
+      const float sa = a == 0 ? S.x : (a == 1 ? S.y : S.z);
+      da = a == 0 ? D.x : (a == 1 ? D.y : D.z);
       ns = da > 0.0f ? -sa : sa;
       const float px = S.x * D.x, py = S.y * D.y, pz = S.z * D.z;
       const float rd = ((a == 0 ? -px : px) + (a == 1 ? -py : py)) + (a == 2 ? -pz : pz);
@@ -571,10 +654,10 @@ __device__ __forceinline__ bool cert_shade_hit(const Ctx& c, const Ray& ray, con
       const float specular = mat_ks(m, TEX) * gpow(gmax(rd, 0.0f), mat_exp(m, TEX));
       lit = kAmbient + diffuse + specular;
     } else {
-      lit = lit_brightness<TEX>(hh, S, ray.dir);
+      lit = lit_generic();
     }
   } else {
-    lit = lit_brightness<TEX>(hh, S, ray.dir);
+    lit = lit_generic();
   }
   float brightness = kAmbient;
   if (lit != kAmbient && !shadow_free_hit(h.byte, TEX)) {  // otherwise the brightness is the ambient term (or irrelevant)
@@ -591,18 +674,65 @@ __device__ __forceinline__ bool cert_shade_hit(const Ctx& c, const Ray& ray, con
     // every octant volume holds the same voxel bytes)
     const uint32_t sob =
         KAX ? sk->sun_obase : ((S.x < 0.0f ? 1u : 0u) | (S.y < 0.0f ? 2u : 0u) | (S.z < 0.0f ? 4u : 0u)) * c.ostride;
-    const uint32_t t0 = path_texel(c, ax + (KAX ? sk->sun_step[0] : (S.x > 0.0f ? 1 : -1)), ay + (KAX ? sk->sun_step[1] : (S.y > 0.0f ? 1 : -1)),
-                                   az + (KAX ? sk->sun_step[2] : (S.z > 0.0f ? 1 : -1)), sob);
-    f3 ed;
-    if (!cert_start(hh.point, ray.dir, S, c.sun_rcp, h.axis, h.eu, ax, ay, az, ed)) {
-      CERT_DIAG(6);
-      return false;
+    // (KAX: by start_texel, path_texel's value without its branch: the merge behind the branch made the wave wait
+    // for the load at once, and nothing overlapped it)
+    const int tx = ax + (KAX ? sk->sun_step[0] : (S.x > 0.0f ? 1 : -1)), ty = ay + (KAX ? sk->sun_step[1] : (S.y > 0.0f ? 1 : -1)),
+              tz = az + (KAX ? sk->sun_step[2] : (S.z > 0.0f ? 1 : -1));
+    const uint32_t t0 = KAX ? start_texel(c, tx, ty, tz, sob) : path_texel(c, tx, ty, tz, sob);
+    if (KAX && PHASE_STOP(7)) {  // phase budget: the record, the lit term and the start's cell and texel as the colour
+      color = mk(lit + hh.len, hh.point.x + hh.point.y + hh.point.z + da, float(int(t0) + ax + ay + az));
+      return true;
     }
-    const uint32_t n = uint32_t(c.n);
-    if (uint32_t(ax) >= n || uint32_t(ay) >= n || uint32_t(az) >= n) { CERT_DIAG(7); return false; }
-    if (cert_event<true>(cell_texel(c, ax, ay, az, sob) & kVoxMask, 0u)) { CERT_DIAG(7); return false; }
-    const CertResult s = cert_walk<true, LEAN>(c, hh.point, S, c.sun_rcp, c.max_len - hh.len, ax, ay, az,
-                                         h.eu, ed, hh.len, 0u, t0, nullptr, KAX ? sk : nullptr);
+    f3 ed;
+    CertShadowK sh;
+    // (KAX: the start's verdict and the air cell's are one flag, and the lanes either of them stops leave
+    // together below: each `return` of its own was a region with its saved lane mask, spilled across the walk)
+    bool go = true;
+    if constexpr (KAX) {
+      go = cert_start_sun(hh.point, ray.dir, da, sk, c.sun_rcp, h.axis, h.eu, ax, ay, az, ed, sh);
+      if (!go) CERT_DIAG(6);
+    } else {
+      if (!cert_start(hh.point, ray.dir, S, c.sun_rcp, h.axis, h.eu, ax, ay, az, ed)) {
+        CERT_DIAG(6);
+        return false;
+      }
+    }
+    if (KAX && PHASE_STOP(8)) {  // phase budget: + the shadow's start
+      color = mk(lit + hh.len + ed.x + ed.y + ed.z, sh.sig.x + sh.sig.y + sh.sig.z, float(int(t0) + ax + ay + az));
+      return true;
+    }
+    // The air cell (ax, ay, az) must be inside the volume and hold no shadow event. It is the cell the primary
+    // walk was in before its last crossing, and the walk's loop has proved both of every cell it moved into:
+    //  - a jump lands inside its box, and a box lies inside the volume and holds empty cells only (byte 0: the
+    //    boxes of the skip field, vrt_walk.h; cert_walk's landing argument);
+    //  - a crossing that does not end the walk entered a cell that is not outside (`outside` ends the walk)
+    //    and whose byte is the medium's, 0 (`ev` ends it: the primary walks in air);
+    //  - the walk's cells never repeat (each coordinate moves one way), so a cell that is not the start cell
+    //    was moved into, by one of the two.
+    // Byte 0 is no shadow event, and every octant volume holds the same bytes. What the loop has not sampled is
+    // the start cell itself (a hit at the first crossing, no jump before it: a camera inside a solid voxel, a
+    // wall right in front of it): there the test stays. KAX knows the start cell only as the launch's constant
+    // (kSetupCell: every pixel's walk starts in start_cell, cert_pixel); without that proof every lane tests.
+    bool air_known = false;
+    if constexpr (KAX)
+      air_known = (sk->setup & kSetupCell) != 0u &&
+                  ((ax ^ sk->start_cell[0]) | (ay ^ sk->start_cell[1]) | (az ^ sk->start_cell[2])) != 0;
+    if constexpr (KAX) {
+      if (go && !air_known) {  // (the load stays behind the bounds test: the cell's address exists only inside the volume)
+        const uint32_t n = uint32_t(c.n);
+        go = max(max(uint32_t(ax), uint32_t(ay)), uint32_t(az)) < n;
+        if (go) go = !cert_event<true>(cell_texel(c, ax, ay, az, sob) & kVoxMask, 0u);
+        if (!go) CERT_DIAG(7);
+      }
+      if (!go) return false;
+    } else {
+      const uint32_t n = uint32_t(c.n);
+      if (uint32_t(ax) >= n || uint32_t(ay) >= n || uint32_t(az) >= n) { CERT_DIAG(7); return false; }
+      if (cert_event<true>(cell_texel(c, ax, ay, az, sob) & kVoxMask, 0u)) { CERT_DIAG(7); return false; }
+    }
+    const CertResult s = cert_walk<true, LEAN, true, KAX>(c, hh.point, S, c.sun_rcp, c.max_len - hh.len, ax, ay, az,
+                                                          h.eu, ed, hh.len, 0u, t0, nullptr, KAX ? sk : nullptr,
+                                                          KAX ? &sh : nullptr);
     if (LEAN && (PHASE_STOP(4) || PHASE_STOP(5))) {  // phase budget: the shadow walk's result as the colour
       color = mk(s.u + float(s.res), lit + float(s.cx), 0.0f);
       return true;
@@ -614,9 +744,17 @@ __device__ __forceinline__ bool cert_shade_hit(const Ctx& c, const Ray& ray, con
     CERT_DIAG(4);
   }
   if (!TEX) col = get_color<false>(c, hh);  // textured: the certified texel (cert_texel)
-  color.x = mixf(color.x, col.x * col.w * brightness, ray.energy);
-  color.y = mixf(color.y, col.y * col.w * brightness, ray.energy);
-  color.z = mixf(color.z, col.z * col.w * brightness, ray.energy);
+  if constexpr (KAX) {
+    // The primary hit of a pixel: the colour so far is +0 and the energy 1 (cert_pixel), so mixf forms +0 * (1 -
+    // 1) + y * 1 = +0 + y, which is y bit for bit unless y is -0; y = (col_b * col.w) * brightness is a product
+    // of factors that are never negative (a material's or an atlas texel's colour, bytes / 255; brightness >=
+    // the ambient term: diffuse and specular are a non-negative factor times a maximum with 0 and a power).
+    color = mk(col.x * col.w * brightness, col.y * col.w * brightness, col.z * col.w * brightness);
+  } else {
+    color.x = mixf(color.x, col.x * col.w * brightness, ray.energy);
+    color.y = mixf(color.y, col.y * col.w * brightness, ray.energy);
+    color.z = mixf(color.z, col.z * col.w * brightness, ray.energy);
+  }
   return true;
 }
 
@@ -1295,7 +1433,7 @@ __device__ __forceinline__ bool cert_pixel(const Ctx& c0, const Ray& ray0, f3& c
     if constexpr (TREE && !TEX) return cert_tree<NL, LEAN>(c, max_refl, max_transp, ray0, h, color_out, c.ax, ltb);
     return false;
   }
-  const Hit hh = cert_hit_record(ray0, h);
+  const Hit hh = LEAN ? cert_hit_record_primary(ray0, h) : cert_hit_record(ray0, h);
   float4 col = float4();
   if (TEX && !cert_texel(c, ray0, h, hh, col)) return false;
   if constexpr (LEAN) {  // the sun's constants from the launch's arguments, read here, after the primary walk

@@ -16,6 +16,9 @@
 // are meaningless. 0 launch and epilogue only, 1 + ray set-up, 2 + the primary walk's start checks and
 // prologue, 3 + its loop, 4 + lit term, shadow start and the shadow walk's prologue (and the sky of
 // primary misses), 5 + the shadow loop; the full build adds the colour. 6: the full pass without the sky.
+// Phase 4 split (a primary hit's shadow side, cert_shade_hit<.., KAX>): 7 phase 3 + the hit record, the lit
+// term, the start cell and its texel (and the sky), 8 + the shadow's start (cert_start_sun); 4 adds the air
+// cell's test and the shadow walk's prologue.
 #ifdef VRT_PHASE_STOP
 #ifndef VRT_DIAGNOSTIC_BUILD
 #error "VRT_PHASE_STOP is a diagnostic build: use make variant"
