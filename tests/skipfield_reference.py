@@ -1,10 +1,114 @@
-"""The skip field of the packed volume(s) by brute force in NumPy: the one reference of the GPU volume
-tests (tests/test_gpu_volume.py, tests/test_gpu_volume_edit.py) and of the edit plan's CPU test
-(tests/test_volume_edit_plan.py), with the small edit helpers they share. Plain helpers, no tests."""
+"""The skip field of the packed volume(s), restated twice, with the small edit helpers the tests share.
+
+By brute force in NumPy (forward_reference, chebyshev_reference, packed_reference): the reference of
+the GPU volume tests (tests/test_gpu_volume.py, tests/test_gpu_volume_edit.py) and of the edit plan's
+CPU test (tests/test_volume_edit_plan.py) at N <= 32, where the caps clamp nothing and every regional
+box is the whole volume.
+
+By tests/skipfield_fast.c (forward_fast, chebyshev_fast, packed_fast): the largest-empty-cube dynamic
+programme and the 26-neighbour chamfer, which share no algorithm with the kernels or with the brute
+force, equal the brute force at N <= 32 (tests/test_skipfield_fast.py) and reach N = 256, where the
+caps clamp and the boxes are regional (tests/test_gpu_skipfield_caps.py, tests/test_volume_edit_plan.py).
+void256 is the volume of those tests. Plain helpers, no tests."""
+import ctypes as C
+import functools
+import hashlib
+import os
+import subprocess
+
 import numpy as np
 
 CAP = 64  # kDistCap of csrc/vrt_walk.h
 FWD_CAP = 128  # kFwdCap (VRT_FWD_CAP, csrc/vrt_tuning.h)
+UNCAPPED = 255  # the largest cap the fast reference takes: nothing in a 256^3 volume reaches it
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+
+
+# ---- the fast reference (tests/skipfield_fast.c) -------------------------------------------------
+
+@functools.lru_cache(maxsize=None)
+def load_skipfield_fast():
+    """tests/skipfield_fast.c, built once per process into build/skipfield_fast.so, with its ctypes
+    signatures."""
+    so = os.path.join(ROOT, "build", "skipfield_fast.so")
+    os.makedirs(os.path.dirname(so), exist_ok=True)
+    subprocess.check_call(["gcc", "-O2", "-shared", "-fPIC", "-fopenmp", "-o", so,
+                           os.path.join(HERE, "skipfield_fast.c")])
+    L = C.CDLL(so)
+    L.sf_forward.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    L.sf_chebyshev.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    L.sf_packed.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    for fn in (L.sf_forward, L.sf_chebyshev, L.sf_packed):
+        fn.restype = C.c_int
+    return L
+
+
+def volume_bytes(vox, n):
+    v = np.ascontiguousarray(vox, np.uint8).reshape(-1)
+    assert v.size == n ** 3, (v.size, n)
+    return v
+
+
+def forward_fast(vox, n, octant, cap=FWD_CAP):
+    """F of `octant` at every anchor, [z][y][x] n^3 u8 (F, not G: G(w) = max(F(w - s) - 1, 0))."""
+    v, out = volume_bytes(vox, n), np.empty((n, n, n), np.uint8)
+    rc = load_skipfield_fast().sf_forward(v.ctypes.data, n, octant, cap, out.ctypes.data)
+    assert rc == 0, ("sf_forward", rc)
+    return out
+
+
+def chebyshev_fast(vox, n, cap=CAP):
+    """D at every voxel, [z][y][x] n^3 u8."""
+    v, out = volume_bytes(vox, n), np.empty((n, n, n), np.uint8)
+    rc = load_skipfield_fast().sf_chebyshev(v.ctypes.data, n, cap, out.ctypes.data)
+    assert rc == 0, ("sf_chebyshev", rc)
+    return out
+
+
+_volumes = {}   # digest -> bytes, for the cached function's first call
+
+
+@functools.lru_cache(maxsize=3)   # 271 MB per entry at N = 256, octants = 8
+def _packed_fast(digest, n, octants, fwd_cap, dist_cap):
+    v = _volumes.pop(digest)
+    out = np.empty((octants,) + (n + 1,) * 3, np.uint16)
+    rc = load_skipfield_fast().sf_packed(v.ctypes.data, n, octants, fwd_cap, dist_cap, out.ctypes.data)
+    assert rc == 0, ("sf_packed", rc)
+    out.setflags(write=False)
+    return out
+
+
+def packed_fast(vox, n, octants, fwd_cap=FWD_CAP, dist_cap=CAP):
+    """packed_reference by the fast reference: [octant][z][y][x] (n+1)^3 u16, read-only, cached per
+    volume (by its bytes' digest), layout and caps."""
+    v = volume_bytes(vox, n)
+    digest = hashlib.sha1(v).digest()
+    _volumes[digest] = v
+    try:
+        return _packed_fast(digest, n, octants, fwd_cap, dist_cap)
+    finally:
+        _volumes.pop(digest, None)
+
+
+@functools.lru_cache(maxsize=None)
+def void256():
+    """256^3 bytes, read-only: a void with an off-centre cluster (every in-volume cube of edge >= 129
+    holds the voxel (128, 128, 128), so a centred object would keep kFwdCap from ever clamping), one
+    glass block beside it, two lone voxels and a floor slab. Indexed [z][y][x]."""
+    v = np.zeros((256, 256, 256), np.uint8)
+    v[60:66, 60:66, 60:66] = 1
+    v[60:66, 60:66, 66:72] = 2
+    v[10, 10, 10] = 3
+    v[30, 200, 245] = 200
+    v[:, 20, :] = 3
+    flat = v.reshape(-1)
+    flat.setflags(write=False)
+    return flat
+
+
+# ---- the brute force -----------------------------------------------------------------------------
 
 
 def forward_reference(vox, n, octant):

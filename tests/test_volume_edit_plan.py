@@ -5,12 +5,17 @@ brute-force NumPy G / D of the volume before and after seeded edits changes no t
 Per axis, edit cells [lo, hi), octant step s, FC = kFwdCap, DC = kDistCap: the anchors whose forward
 distance F can change are [lo - (FC-1), hi - 1] (s = +1) or [lo, hi - 1 + (FC-1)] (s = -1); the
 texel G(w) = F(w - s) - 1 shifts that range by s; united with [lo, hi) for the voxel bytes and
-clipped to [0, N). Single layout: [lo - (DC-1), hi - 1 + (DC-1)], clipped."""
+clipped to [0, N). Single layout: [lo - (DC-1), hi - 1 + (DC-1)], clipped.
+
+At N = 16 and 32 the caps' reach exceeds the volume, so every span runs to the volume's face and the
+brute-force cases never try the plan's width; the cases that carry the weight are the N = 256 ones on
+void256, against the fast reference (tests/skipfield_fast.c), where the plans are strict sub-boxes."""
 import numpy as np
 import pytest
 
 import voxelraytracer_amd as vrt
-from skipfield_reference import CAP, FWD_CAP, apply_edit, packed_texels, random_edit
+from skipfield_reference import (CAP, FWD_CAP, apply_edit, chebyshev_fast, forward_fast, packed_fast,
+                                 packed_texels, random_edit, void256)
 
 
 def expected_plan(n, octants, origin, extent):
@@ -82,6 +87,10 @@ def test_plan_rejects_bad_arguments(built, args):
 @pytest.mark.parametrize("scene,n,seed", [("terrain", 16, 3), ("refraction", 16, 2), ("glass_cube", 16, 7),
                                           ("terrain", 32, 10), ("refraction", 32, 11)])
 def test_every_changed_texel_lies_inside_the_plan(built, scene, n, seed, octants):
+    """At these sizes the caps' reach (127 and 63 cells) exceeds the volume, so no span of the plan is cut by
+    a cap (asserted below): the plan is the whole volume in the single layout, and in the octant layout it
+    runs from the edit to the faces behind it, leaving out only texels ahead of the edit. The width of the
+    plan is never tried here; test_changed_texels_at_256 is the case where it is."""
     rng = np.random.default_rng(seed)
     vox = vrt.build_scene(scene, n)
     before = packed_texels(vox, n, octants)
@@ -94,6 +103,12 @@ def test_every_changed_texel_lies_inside_the_plan(built, scene, n, seed, octants
         ext = block.shape[::-1]
         plan = vrt.volume_edit_plan(n, octants, origin, ext)
         assert len(plan) == octants
+        for o, row in enumerate(plan):   # no span is cut by a cap, every one runs to the volume's face
+            for a in range(3):
+                if octants == 1 or not o >> a & 1:
+                    assert row[a] == 0, (o, a, row)
+                if octants == 1 or o >> a & 1:
+                    assert row[3 + a] == n, (o, a, row)
         for o, (x0, y0, z0, x1, y1, z1) in enumerate(plan):
             diff = before[o] != after[o]
             assert diff.any(), "an edit that changes emptiness changes texels"
@@ -101,3 +116,69 @@ def test_every_changed_texel_lies_inside_the_plan(built, scene, n, seed, octants
             inside[z0:z1, y0:y1, x0:x1] = True
             assert not np.any(diff & ~inside), (origin, ext, o, np.argwhere(diff & ~inside)[:4])
         vox, before = new, after
+
+
+N256 = 256
+CENTRE = (128, 128, 128)
+EDITS_256 = {   # name: (origin (x, y, z), block [z][y][x]) on void256
+    "set_centre": (CENTRE, np.full((1, 1, 1), 1, np.uint8)),
+    "set_off_centre": ((200, 150, 90), np.full((1, 1, 1), 1, np.uint8)),
+    "carve_floor": ((100, 20, 100), np.zeros((4, 2, 3), np.uint8)),   # 3 x 2 x 4 cells, y = 20 and 21
+    "clear_lone": ((10, 10, 10), np.zeros((1, 1, 1), np.uint8)),
+}
+
+
+@pytest.mark.parametrize("octants", [8, 1])
+@pytest.mark.parametrize("name", list(EDITS_256))
+def test_changed_texels_at_256(built, name, octants):
+    """void256 against the fast reference: (a) some octant's plan is a strict sub-range of every axis, so
+    the case can fail; (b) no changed texel lies outside the plan; (c) for the voxel set at the centre the
+    changed texels touch all six faces of the plan in every octant whose far anchor (127 cells behind the
+    edit on every axis) had F = 128 before, which then holds 127; in the single layout, where the cells 63
+    away go from D = 64 to 63, five faces (the floor slab keeps D low towards the sixth). The plan is tight:
+    it is not an over-wide box hiding an under-wide one."""
+    n = N256
+    origin, block = EDITS_256[name]
+    vox = void256()
+    new = apply_edit(vox, n, origin, block)
+    assert np.any((new != 0) != (vox != 0))
+    before, after = packed_fast(vox, n, octants), packed_fast(new, n, octants)
+    ext = block.shape[::-1]
+    plan = vrt.volume_edit_plan(n, octants, origin, ext)
+    assert len(plan) == octants
+    assert any(all(row[a] > 0 or row[3 + a] < n for a in range(3)) for row in plan), plan   # (a)
+    boxes = []
+    for o, (x0, y0, z0, x1, y1, z1) in enumerate(plan):
+        diff = before[o, :n, :n, :n] != after[o, :n, :n, :n]
+        assert diff.any(), "an edit that changes emptiness changes texels"
+        zz, yy, xx = np.nonzero(diff)
+        box = (int(xx.min()), int(yy.min()), int(zz.min()), int(xx.max()) + 1, int(yy.max()) + 1, int(zz.max()) + 1)
+        assert all(box[a] >= plan[o][a] and box[3 + a] <= plan[o][3 + a] for a in range(3)), (o, box, plan[o])   # (b)
+        inside = np.zeros_like(diff)
+        inside[z0:z1, y0:y1, x0:x1] = True
+        assert not np.any(diff & ~inside), (origin, ext, o, np.argwhere(diff & ~inside)[:4])
+        boxes.append(box)
+    if name != "set_centre":
+        return
+    if octants == 1:   # (c)
+        far = CENTRE[0] + (CAP - 1)
+        assert chebyshev_fast(vox, n)[far, far, far] == CAP and chebyshev_fast(new, n)[far, far, far] == CAP - 1
+        # five faces of the plan are touched; towards the floor slab (y = 20) D(v) <= y - 20 already, and the
+        # new voxel is nearer than that only where 128 - y < y - 20, from y = 75 on
+        lo, hi = CENTRE[0] - (CAP - 1), CENTRE[0] + CAP
+        assert plan == [(lo, lo, lo, hi, hi, hi)] and boxes == [(lo, 75, lo, hi, hi, hi)], (boxes, plan)
+        return
+    want = []
+    for o in range(8):
+        ax, ay, az = (CENTRE[a] - (FWD_CAP - 1) * (-1 if o >> a & 1 else 1) for a in range(3))
+        f0, f1 = int(forward_fast(vox, n, o)[az, ay, ax]), int(forward_fast(new, n, o)[az, ay, ax])
+        if f0 == FWD_CAP:
+            assert f1 == FWD_CAP - 1, (o, f0, f1)
+            want.append(o)
+        else:
+            assert f1 == f0, (o, f0, f1)
+    # the far anchor's cube holds the floor slab where the y step is +1 (y in [1, 128]), the cluster or the
+    # voxel at (10, 10, 10) in octants 0 and 4, and the byte 200 at (245, 200, 30) in octant 3
+    assert want == [2, 6, 7], want
+    tight = [o for o in range(8) if boxes[o] == tuple(plan[o])]
+    assert set(want) <= set(tight), (want, tight, boxes, plan)
