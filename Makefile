@@ -9,12 +9,14 @@ LIBDIR := voxelraytracer_amd/_lib
 HIPFLAGS := -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -ffp-contract=off \
             -fhip-fp32-correctly-rounded-divide-sqrt -fno-slp-vectorize -Iinclude -Wall
 CSRC := voxelraytracer_amd/csrc
-# the C-ABI context, one file per concern; vrt_launch_consts.cpp and vrt_bands.cpp are plain
-# host arithmetic (no HIP or RCCL call) but take the same flags: -ffp-contract=off is part of their contract
+# the C-ABI context, one file per concern; vrt_launch_consts.cpp, vrt_bands.cpp and
+# vrt_skipfield_plan.cpp are plain host arithmetic (no HIP or RCCL call) but take the same flags:
+# -ffp-contract=off is part of their contract
 SRC := $(CSRC)/vrt_render.hip $(CSRC)/vrt_context.cpp $(CSRC)/vrt_launch_consts.cpp $(CSRC)/vrt_bands.cpp \
-       $(CSRC)/vrt_launch.cpp $(CSRC)/vrt_volume.cpp $(CSRC)/vrt_frames.cpp $(CSRC)/vrt_band_api.cpp \
-       $(CSRC)/vrt_queries.cpp $(CSRC)/vrt_host.cpp
+       $(CSRC)/vrt_skipfield_plan.cpp $(CSRC)/vrt_launch.cpp $(CSRC)/vrt_volume.cpp $(CSRC)/vrt_frames.cpp \
+       $(CSRC)/vrt_band_api.cpp $(CSRC)/vrt_queries.cpp $(CSRC)/vrt_filters.cpp $(CSRC)/vrt_host.cpp
 HDR := include/vrt.h $(CSRC)/vrt_internal.h $(CSRC)/vrt_context.h $(CSRC)/vrt_bands.h \
+       $(CSRC)/vrt_instances.h $(CSRC)/vrt_skipfield_plan.h \
        $(CSRC)/vrt_tuning.h $(CSRC)/vrt_diag.h $(CSRC)/vrt_math.h \
        $(CSRC)/vrt_walk.h $(CSRC)/vrt_cert.h $(CSRC)/vrt_aux_kernels.h \
        $(CSRC)/vrt_skipfield_kernels.h $(CSRC)/vrt_query_kernels.h $(CSRC)/vrt_trace_kernels.h \

@@ -137,7 +137,7 @@ __device__ __forceinline__ LateKArgs* late_kargs() {
   return ka;
 }
 // The shadow walk's functions of the sun alone are such arguments (KArgs::sun_*, formed once per launch
-// on the host, sun_consts in vrt_context.cpp: IEEE single operations in the kernel's order, no
+// on the host, sun_consts in vrt_launch_consts.cpp: IEEE single operations in the kernel's order, no
 // contraction): cert_shade_hit<.., KAX> reads them through a LateKArgs pointer and hands it on to its
 // cert_walk<.., KSUN>. sun_ok is fast_path_ok(sun_n); the other fields mean something only then.
 
@@ -1366,7 +1366,7 @@ __device__ __forceinline__ bool cert_pixel(const Ctx& c0, const Ray& ray0, f3& c
     // puts that function, unchanged, behind one region.
     // (tests/test_cert_start_lit_forms.py: both forms over the sign octants and the edge positions)
     //
-    // kSetupCell (KArgs::setup, wave-uniform; cert_launch_consts in vrt_context.cpp): the host has proved
+    // kSetupCell (KArgs::setup, wave-uniform; cert_launch_consts in vrt_launch_consts.cpp): the host has proved
     // that every pixel's P_b of the launch lies strictly inside one cell c_b of the volume, at least 2^-9
     // from its planes. Then floor(P_b) = c_b and floor(-P_b) = -c_b - 1 (P_b is no integer), so fl_b + 1
     // is a select of two launch constants and the cell is c_b whatever the sign; the bounds hold; the plane

@@ -75,10 +75,20 @@ static hipError_t shard_init(Shard& s, int device) {
   return e;
 }
 
-// The image size limits of every entry point that takes a camera
-int check_image(vrt_ctx* ctx, const vrt_camera* cam) {
-  if (cam->width <= 0 || cam->height <= 0 || cam->width > 32768 || cam->height > 32768)
-    return fail(ctx, VRT_ERR_INVALID, "bad image size");
+// The image size limits of every entry point that takes a camera or an image size
+int check_image(vrt_ctx* ctx, int32_t width, int32_t height) {
+  if (width <= 0 || height <= 0 || width > 32768 || height > 32768) return fail(ctx, VRT_ERR_INVALID, "bad image size");
+  return VRT_OK;
+}
+int check_image(vrt_ctx* ctx, const vrt_camera* cam) { return check_image(ctx, cam->width, cam->height); }
+
+// A band of rows [row0, row0 + rows) of a width x height image in buffers of `pitch` pixels per row (the ID pass,
+// the reprojection, a spatial pass). pitch_first: which of the two a call with both wrong reports (the spatial
+// pass has always named the pitch, the others the band)
+int check_band(vrt_ctx* ctx, int32_t width, int32_t height, int32_t row0, int32_t rows, int64_t pitch, bool pitch_first) {
+  const bool bad_band = rows < 0 || row0 < 0 || int64_t(row0) + rows > height, bad_pitch = pitch < width;
+  if (bad_pitch && (pitch_first || !bad_band)) return fail(ctx, VRT_ERR_INVALID, "row pitch must be >= the image width");
+  if (bad_band) return fail(ctx, VRT_ERR_INVALID, "row band outside the image");
   return VRT_OK;
 }
 

@@ -280,7 +280,10 @@ inline hipStream_t main_stream(const Shard& s) { return s.ls[0][0]; }
 
 // ---- vrt_context.cpp: checks shared by the entry points
 int check_render_args(vrt_ctx* ctx, const vrt_camera* cam, const vrt_params* p);
+int check_image(vrt_ctx* ctx, int32_t width, int32_t height);
 int check_image(vrt_ctx* ctx, const vrt_camera* cam);
+int check_band(vrt_ctx* ctx, int32_t width, int32_t height, int32_t row0, int32_t rows, int64_t pitch,
+               bool pitch_first = false);
 int check_pixel_list(vrt_ctx* ctx, const vrt_camera* cam, const int32_t* pixels, int32_t count);
 
 // ---- vrt_volume.cpp
@@ -304,6 +307,17 @@ void launch_timing_events(vrt_ctx* ctx, hipEvent_t& begin, hipEvent_t& end);
 
 // ---- vrt_frames.cpp
 int ensure_stage(vrt_ctx* ctx, size_t bytes);
+
+// ---- vrt_queries.cpp: the ID pass, as the filters of vrt_filters.cpp use it
+// Arguments shared by vrt_render_ids* and the reprojection (which takes the band's ids and depth), in the pick's
+// order. rows / pitch: the band (the synchronous form passes the whole frame's); device: the buffers' alignment is
+// checked (the kernels' 8- and 4-byte stores)
+int check_ids(vrt_ctx* ctx, const vrt_camera* cam, const vrt_params* p, int32_t row0, int32_t rows, int64_t pitch,
+              const void* ids, const void* depth, bool device);
+// One ID pass over rows [row0, row0 + rows) (rows >= 1) on `st`: one launch of the exact ID kernel, no
+// allocation, no host synchronisation
+int enqueue_ids(vrt_ctx* ctx, const vrt_camera* cam, const vrt_params* p, int32_t row0, int32_t rows, int32_t pitch,
+                vrt_pixel_id* d_ids, float* d_depth, hipStream_t st);
 
 }  // namespace vrt
 

@@ -8,6 +8,7 @@
 #include <cstdint>
 
 #include "vrt.h"
+#include "vrt_skipfield_plan.h"
 #include "vrt_tuning.h"
 
 namespace vrt {
@@ -138,10 +139,14 @@ constexpr uint32_t kDeferDense = 32;        // deferred pixels from which a wave
 
 // ---- launches (vrt_render.hip); all asynchronous on `s` ------------------------------------
 
-// render_kernel: the instance is chosen from (stats, a.textured, a.cert); grid = a.tiles, or
-// 8 * a.ord_q + a.tiles with a tile order (a.order). cnt_rep: the counter replicas (stats launches).
+// render_kernel, or for a deferred pair (a.defer on a stats-free a.cert 2 launch) the certified pass and then the
+// exact pass over the pixels it left: the instances are rows of vrt_instances.h, chosen there (choose_instances)
+// from stats, a.textured, a.cert, a.tree, a.order, a.defer, a.nframes and a.exact_fat. grid = a.tiles, or
+// 8 * a.ord_q + a.tiles with a tile order (a.order); the pair's grids: at the launch. cnt_rep: the counter
+// replicas (stats launches).
 // ev_begin / ev_end (optional, timing events) are recorded when the kernel starts and ends on
-// the device (hipExtLaunchKernelGGL), not when the host enqueues it.
+// the device (hipExtLaunchKernelGGL), not when the host enqueues it; a pair records begin with its first
+// kernel and end with its second.
 void launch_render(const KArgs& a, bool stats, const uint16_t* vox, float4* out, vrt_hit* hit,
                    unsigned long long* cnt_rep, hipStream_t s, hipEvent_t ev_begin = nullptr,
                    hipEvent_t ev_end = nullptr);
@@ -165,7 +170,7 @@ void launch_ray_trace(const KArgs& a, int32_t kind, const uint16_t* vox, const v
 // one-wave workgroup. ev_begin / ev_end: optional device timestamps, as launch_render's
 void launch_render_ids(const KArgs& a, const uint16_t* vox, vrt_pixel_id* ids, float* depth, hipStream_t s,
                        hipEvent_t ev_begin = nullptr, hipEvent_t ev_end = nullptr);
-// reproject_kernel (vrt_reproject_kernels.h): the band `a` describes (make_args with row_step 1, as
+// reproject_kernel and its two other fetch forms (vrt_reproject_kernels.h): the band `a` describes (make_args with row_step 1, as
 // launch_render_ids; a.pitch pixels between band rows of raw, ids, depth, out and src), one launch, a 16x16
 // tile per workgroup of kReprojWg threads. prev / prev_ids: the whole previous frame, prev_pitch pixels
 // between rows, both null for "no history"; src may be null. ev_begin / ev_end: optional device timestamps
@@ -182,14 +187,11 @@ struct ReprojArgs {
   int32_t* src;
 };
 constexpr int kReprojWg = 256;
-void launch_reproject(const KArgs& a, const ReprojArgs& r, hipStream_t s, hipEvent_t ev_begin = nullptr,
-                      hipEvent_t ev_end = nullptr);
-// The same launch with a fetch mode and an optional tap-mask buffer (one byte per band pixel at a.pitch):
-// VRT_FETCH_NEAREST without taps is launch_reproject itself (reproject_kernel), with taps
-// reproject_nearest_taps_kernel (the same pixels plus the byte); VRT_FETCH_BILINEAR is
-// reproject_bilinear_kernel. One launch either way; fetch is one of the two modes (the caller checks)
-void launch_reproject_fetch(const KArgs& a, const ReprojArgs& r, int32_t fetch, uint8_t* taps, hipStream_t s,
-                            hipEvent_t ev_begin = nullptr, hipEvent_t ev_end = nullptr);
+// fetch (one of the two modes: the caller checks) and taps, an optional tap-mask buffer (one byte per band pixel
+// at a.pitch), choose the kernel: VRT_FETCH_NEAREST without taps reproject_kernel, with taps
+// reproject_nearest_taps_kernel (the same pixels plus the byte); VRT_FETCH_BILINEAR reproject_bilinear_kernel
+void launch_reproject(const KArgs& a, const ReprojArgs& r, int32_t fetch, uint8_t* taps, hipStream_t s,
+                      hipEvent_t ev_begin = nullptr, hipEvent_t ev_end = nullptr);
 // spatial_direct_kernel / spatial_lds_kernel (vrt_spatial_kernels.h): one à-trous pass over rows [row0, row0 +
 // rows) of a width x height frame; every buffer whole-frame indexed, pixel (x, y) at [y * pitch + x]. keep and
 // count may be null. nlog: log2 of the resident volume's edge (the PLANE guide's key). One launch, a 16x16 tile
@@ -212,17 +214,15 @@ constexpr bool spatial_lds_form(int32_t step) {
 void launch_spatial(const SpatialArgs& a, hipStream_t s, hipEvent_t ev_begin = nullptr, hipEvent_t ev_end = nullptr);
 // fold the counter replicas into dst (accumulating) and re-zero them
 void launch_reduce_counters(unsigned long long* rep, unsigned long long* dst, hipStream_t s);
-// in-place edit of the box [lo, lo + ext) (vrt_update_volume_region), inside [0, N)^3:
-// the packed texels an edit may change, per packed volume o: out[o*6 + 0..5] = {x0,y0,z0,x1,y1,z1}
-// (half-open, in [0, N)^3; host arithmetic)
-int volume_edit_plan(int32_t n, int octants, const int32_t lo[3], const int32_t ext[3], int32_t* out);
+// in-place edit of the box [lo, lo + ext) (vrt_update_volume_region), inside [0, N)^3 (the texels it may change:
+// volume_edit_plan, vrt_skipfield_plan.h):
 // the box-local bytes `box` (device, x fastest) into the canonical volume; counts[0..4] (accumulating)
 // = the box's glass and non-empty voxels before, the same after, cells whose emptiness changed
 void launch_edit_apply(const uint8_t* box, uint8_t* vox, uint32_t n, const int32_t lo[3], const int32_t ext[3],
                        unsigned long long* counts, hipStream_t s);
 // the kernel's packed volume(s) from the canonical N^3 bytes after a change inside the box [lo, lo + ext):
 // 8 octant forward-distance volumes (octants == 8; tmp = 3 N^3 bytes) or one centred-distance volume
-// (tmp = 2 N^3 bytes), rebuilt by passes over the plan's boxes. An upload is the box [0, N)^3 (every
+// (tmp = 2 N^3 bytes), rebuilt by the passes of skipfield_passes (vrt_skipfield_plan.h) in its order. An upload is the box [0, N)^3 (every
 // texel, plane N included); distances = false (no cell's emptiness changed): the voxel bytes of the
 // box only
 void launch_volume_edit_passes(const uint8_t* vox, uint8_t* tmp, uint16_t* packed, uint32_t n, int octants,

@@ -1,7 +1,8 @@
 // vrt_render.hip — gfx950 HIP kernels for the per-pixel program of res/shaders/voxel.glsl; the
-// C-ABI context around them is vrt_context.cpp (include/vrt.h). One translation unit: this file
-// holds the pixel epilogue, the tile order, the primary ray, the bounce-stack exact_pixel, the two
-// frame kernels and the host launch wrappers; the rest is in the headers included below, in
+// C-ABI context around them is vrt_context.h and its vrt_*.cpp files (include/vrt.h). One translation unit: this
+// file holds the pixel epilogue, the tile order, the primary ray, the bounce-stack exact_pixel, the two
+// frame kernels and the host launch wrappers (their instance choice is vrt_instances.h, the boxes of the
+// skip-field passes vrt_skipfield_plan.cpp: host arithmetic); the rest is in the headers included below, in
 // dependency order (vrt_tuning.h through vrt_internal.h), and in vrt_query_kernels.h,
 // vrt_trace_kernels.h, vrt_ids_kernels.h and vrt_reproject_kernels.h (the ray-query, shaded ray-query,
 // ID-pass and reprojected-filter kernels, included after the primary ray and exact_pixel they call),
@@ -19,15 +20,19 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "vrt.h"
 #include "vrt_internal.h"
+#include "vrt_instances.h"
 #include "vrt_diag.h"
 #include "vrt_math.h"
 #include "vrt_walk.h"
@@ -233,7 +238,7 @@ __device__ __forceinline__ bool div3_lean_ranges(float x, float y, float z, floa
 
 // LEAN (the certified pass's instances): the quantities that are the same for every pixel of the launch come
 // from the host (KArgs::fw .. max_len2, and behind the wave-uniform flags of KArgs::setup, each a host proof
-// per launch, cert_launch_consts in vrt_context.cpp):
+// per launch, cert_launch_consts in vrt_launch_consts.cpp):
 //  - kSetupW: the w column is not formed: n4.w and f4.w are the launch's wn and wf bit for bit (the x and y
 //    terms are absorbed by the z term's rounding), their reciprocals the host's, and the tests of d proved;
 //  - kSetupLen: the squared length of vdir is inside normalize3's general range and away from its near-one
@@ -839,15 +844,6 @@ __global__ void __launch_bounds__(64, exact_cap_waves(kExactVgprs))
                              float4* __restrict__ out) {
   exact_pass_body<false, CERT, SB, FB>(kernel_kargs(), vox, out);
 }
-using ExactPassFn = void (*)(KArgs, const uint16_t*, float4*);
-// the colour whole-frame instance of a launch: under the cap where one is set (CAP: kExactVgprs)
-template <int CAP>
-static ExactPassFn exact_pass_whole_frame(bool fb) {
-  if constexpr (CAP == 0)
-    return fb ? exact_pass_kernel<false, 2, kExactWaves, kSparseBatch, true> : exact_pass_kernel<false, 2>;
-  else
-    return fb ? exact_pass_kernel_capped<2, kSparseBatch, true> : exact_pass_kernel_capped<2, kSparseBatch, false>;
-}
 
 }  // namespace vrt
 
@@ -866,69 +862,78 @@ namespace vrt {
 
 // ------------------------------------------------------------------------------- launches --
 // Host wrappers of the kernels above, of vrt_aux_kernels.h, vrt_skipfield_kernels.h,
-// vrt_query_kernels.h and vrt_trace_kernels.h (vrt_internal.h); the C-ABI context is vrt_context.cpp.
+// vrt_query_kernels.h and vrt_trace_kernels.h (vrt_internal.h); the C-ABI context around them is the
+// vrt_*.cpp files of vrt_context.h.
 
+// Every launch of this file: `kern` over grid x block with lds_bytes of dynamic LDS on `s`, its arguments
+// converted to the kernel's parameter types. ev_begin / ev_end (either may be null) are recorded when the kernel
+// starts / ends on the device, which takes the Ext form of the launch: used exactly when an event is given.
+template <class T>
+using KernelArg = const std::common_type_t<T>&;
+template <class... P>
+static void launch_kernel(void (*kern)(P...), dim3 grid, dim3 block, uint32_t lds_bytes, hipStream_t s,
+                          hipEvent_t ev_begin, hipEvent_t ev_end, KernelArg<P>... args) {
+  if (ev_begin || ev_end)
+    hipExtLaunchKernelGGL(kern, grid, block, lds_bytes, s, ev_begin, ev_end, 0, args...);
+  else
+    hipLaunchKernelGGL(kern, grid, block, lds_bytes, s, args...);
+}
 // workgroups of 256 for a grid-stride loop over `items`
 static unsigned grid_blocks(uint64_t items) { return unsigned(std::min<uint64_t>((items + 255) / 256, 16384)); }
+// the untimed launches of such a loop (the kernels of 256 threads that stride over `items` cells)
+template <class... P>
+static void launch_cells(void (*kern)(P...), uint64_t items, hipStream_t s, KernelArg<P>... args) {
+  launch_kernel(kern, dim3(grid_blocks(items)), dim3(256), 0, s, nullptr, nullptr, args...);
+}
+
+// The kernel of every row of vrt_instances.h, built from the row's own fields
+using RenderFn = void (*)(KArgs, const uint16_t*, float4*, vrt_hit*, unsigned long long*);
+using ExactPassFn = void (*)(KArgs, const uint16_t*, float4*);
+template <size_t I>
+constexpr RenderFn render_instance() {
+  constexpr RenderInstance r = kRenderInstances[I];
+  return render_kernel<r.stats, r.tex, r.cert, r.ord, r.defer, r.fb, r.tree>;
+}
+template <size_t I>
+constexpr ExactPassFn exact_instance() {
+  constexpr ExactInstance r = kExactInstances[I];
+  if constexpr (r.capped) {
+    static_assert(!r.tex, "the VGPR cap is the colour instances'");
+    return exact_pass_kernel_capped<r.cert, r.sparse_batch, r.fb>;
+  } else {
+    return exact_pass_kernel<r.tex, r.cert, r.waves, r.sparse_batch, r.fb>;
+  }
+}
+template <size_t... I>
+static std::array<RenderFn, sizeof...(I)> render_table(std::index_sequence<I...>) {
+  return {render_instance<I>()...};
+}
+template <size_t... I>
+static std::array<ExactPassFn, sizeof...(I)> exact_table(std::index_sequence<I...>) {
+  return {exact_instance<I>()...};
+}
+static const auto kRenderKernels = render_table(std::make_index_sequence<kRenderInstanceCount>());
+static const auto kExactKernels = exact_table(std::make_index_sequence<kExactInstanceCount>());
 
 void launch_render(const KArgs& a, bool stats, const uint16_t* vox, float4* out, vrt_hit* hit,
                    unsigned long long* cnt_rep, hipStream_t s, hipEvent_t ev_begin, hipEvent_t ev_end) {
-  const dim3 grid(a.order ? kOrdClasses * a.ord_q + a.tiles : a.tiles);
-  // stats-free colour-only frames (vrt_set_certified): certified pixels (a.cert 2), certified
-  // exact-path rays only (1: the certified primary's registers would slow glass-heavy frames by
-  // ~5 %), exact walks only (0)
-  // textured frames: the hit colour needs the exact hit point, so every pixel takes the exact
-  // walk; its shadow rays are certified walks where they settle (CERT 1, texture-independent)
-  if (a.defer && !stats && a.cert == 2) {
-    // certified pass, then the exact pass over the pixels it deferred (no tile order: the
-    // certified pass has no long waves)
-    // the certified pass's grid: tile columns x tile rows x frames (render_kernel reads its tile
-    // from the workgroup id's components); the same workgroups in the same dispatch order as a.tiles
-    const dim3 g1(a.tiles_x, a.frame_tiles / a.tiles_x, uint32_t(a.nframes)),
-        g2(a.exact_grid ? a.exact_grid
-                        : std::max(64u, a.tiles * uint32_t(kWgWaves) / (a.textured ? kDeferGridDiv : kDeferGridDivColor)));
-    // frame batches (a.nframes > 1): their own instances
-    const bool fb = a.nframes > 1;
-    auto k1 = a.textured ? (fb ? render_kernel<false, true, 2, false, true, true> : render_kernel<false, true, 2, false, true>)
-              : a.tree   ? (fb ? render_kernel<false, false, 2, false, true, true, true>
-                               : render_kernel<false, false, 2, false, true, false, true>)
-                         : (fb ? render_kernel<false, false, 2, false, true, true> : render_kernel<false, false, 2, false, true>);
-    ExactPassFn k2 = a.textured ? (fb ? exact_pass_kernel<true, 1, kExactWaves, kSparseBatchTex, true>
-                                      : exact_pass_kernel<true, 1, kExactWaves, kSparseBatchTex>)
-                     : a.exact_fat ? (fb ? exact_pass_kernel<false, 2, kFatWaves, kSparseBatchFat, true>
-                                         : exact_pass_kernel<false, 2, kFatWaves, kSparseBatchFat>)
-                                   : exact_pass_whole_frame<kExactVgprs>(fb);
-    const uint32_t pad = a.tree ? 0u : kDeferLdsPad;  // (an occupancy A/B knob, vrt_tuning.h)
-    if (ev_begin)
-      hipExtLaunchKernelGGL(k1, g1, dim3(kWgThreads), pad, s, ev_begin, nullptr, 0, a, vox, out, hit, cnt_rep);
-    else
-      hipLaunchKernelGGL(k1, g1, dim3(kWgThreads), pad, s, a, vox, out, hit, cnt_rep);
-    if (ev_end)
-      hipExtLaunchKernelGGL(k2, g2, dim3(64), 0, s, nullptr, ev_end, 0, a, vox, out);
-    else
-      hipLaunchKernelGGL(k2, g2, dim3(64), 0, s, a, vox, out);
+  const InstanceChoice c = choose_instances(stats, a.textured != 0, a.cert, a.tree != 0, a.order != nullptr,
+                                            a.defer != nullptr, a.nframes, a.exact_fat != 0);
+  const RenderFn kern = kRenderKernels[size_t(c.render)];
+  if (c.exact < 0) {
+    const dim3 grid(a.order ? kOrdClasses * a.ord_q + a.tiles : a.tiles);
+    launch_kernel(kern, grid, dim3(kWgThreads), 0, s, ev_begin, ev_end, a, vox, out, hit, cnt_rep);
     return;
   }
-  auto kern = a.textured ? (stats ? render_kernel<true, true>
-                            : a.nframes > 1 ? (a.cert >= 1 ? render_kernel<false, true, 1, false, false, true>
-                                                           : render_kernel<false, true, 0, false, false, true>)
-                                            : (a.cert >= 1 ? render_kernel<false, true, 1> : render_kernel<false, true>))
-                         : (stats ? render_kernel<true, false>
-                            : a.nframes > 1
-                                ? (a.cert == 2 ? (a.order ? render_kernel<false, false, 2, true, false, true>
-                                                          : render_kernel<false, false, 2, false, false, true>)
-                                   : a.cert == 1 ? render_kernel<false, false, 1, false, false, true>
-                                                 : render_kernel<false, false, 0, false, false, true>)
-                                : (a.cert == 2 ? (a.tree ? (a.order ? render_kernel<false, false, 2, true, false, false, true>
-                                                                    : render_kernel<false, false, 2, false, false, false, true>)
-                                                 : a.order ? render_kernel<false, false, 2, true>
-                                                           : render_kernel<false, false, 2>)
-                                   : a.cert == 1 ? render_kernel<false, false, 1>
-                                                 : render_kernel<false, false, 0>));
-  if (ev_begin || ev_end)
-    hipExtLaunchKernelGGL(kern, grid, dim3(kWgThreads), 0, s, ev_begin, ev_end, 0, a, vox, out, hit, cnt_rep);
-  else
-    hipLaunchKernelGGL(kern, grid, dim3(kWgThreads), 0, s, a, vox, out, hit, cnt_rep);
+  // certified pass, then the exact pass over the pixels it deferred.
+  // the certified pass's grid: tile columns x tile rows x frames (render_kernel reads its tile
+  // from the workgroup id's components); the same workgroups in the same dispatch order as a.tiles
+  const dim3 g1(a.tiles_x, a.frame_tiles / a.tiles_x, uint32_t(a.nframes)),
+      g2(a.exact_grid ? a.exact_grid
+                      : std::max(64u, a.tiles * uint32_t(kWgWaves) / (a.textured ? kDeferGridDiv : kDeferGridDivColor)));
+  const uint32_t pad = a.tree ? 0u : kDeferLdsPad;  // (an occupancy A/B knob, vrt_tuning.h)
+  launch_kernel(kern, g1, dim3(kWgThreads), pad, s, ev_begin, nullptr, a, vox, out, hit, cnt_rep);
+  launch_kernel(kExactKernels[size_t(c.exact)], g2, dim3(64), 0, s, nullptr, ev_end, a, vox, out);
 }
 
 void launch_ray_query(const KArgs& a, int32_t kind, const uint16_t* vox, const void* in, uint32_t count,
@@ -938,11 +943,7 @@ void launch_ray_query(const KArgs& a, int32_t kind, const uint16_t* vox, const v
                                            : ray_query_kernel<VRT_CAST_NEAREST>;
   // one lane per query: ceil(count / kQueryWg) workgroups (count <= 2^30)
   const dim3 grid((count + uint32_t(kQueryWg) - 1u) / uint32_t(kQueryWg));
-  if (ev_begin || ev_end)
-    hipExtLaunchKernelGGL(kern, grid, dim3(kQueryWg), 0, s, ev_begin, ev_end, 0, a, vox, in, count,
-                          reinterpret_cast<uint4*>(hits));
-  else
-    hipLaunchKernelGGL(kern, grid, dim3(kQueryWg), 0, s, a, vox, in, count, reinterpret_cast<uint4*>(hits));
+  launch_kernel(kern, grid, dim3(kQueryWg), 0, s, ev_begin, ev_end, a, vox, in, count, reinterpret_cast<uint4*>(hits));
 }
 
 void launch_ray_trace(const KArgs& a, int32_t kind, const uint16_t* vox, const void* in, uint32_t count,
@@ -952,40 +953,23 @@ void launch_ray_trace(const KArgs& a, int32_t kind, const uint16_t* vox, const v
                   : (a.textured ? ray_trace_kernel<kTraceRays, true> : ray_trace_kernel<kTraceRays, false>);
   // one lane per query: ceil(count / kTraceWg) workgroups (count <= 2^30)
   const dim3 grid((count + uint32_t(kTraceWg) - 1u) / uint32_t(kTraceWg));
-  if (ev_begin || ev_end)
-    hipExtLaunchKernelGGL(kern, grid, dim3(kTraceWg), 0, s, ev_begin, ev_end, 0, a, vox, in, count,
-                          reinterpret_cast<uint4*>(out));
-  else
-    hipLaunchKernelGGL(kern, grid, dim3(kTraceWg), 0, s, a, vox, in, count, reinterpret_cast<uint4*>(out));
+  launch_kernel(kern, grid, dim3(kTraceWg), 0, s, ev_begin, ev_end, a, vox, in, count, reinterpret_cast<uint4*>(out));
 }
 
 void launch_render_ids(const KArgs& a, const uint16_t* vox, vrt_pixel_id* ids, float* depth, hipStream_t s,
                        hipEvent_t ev_begin, hipEvent_t ev_end) {
   const dim3 grid(uint32_t(a.width + 7) / 8u, uint32_t(a.rows + 7) / 8u);
-  if (ev_begin || ev_end)
-    hipExtLaunchKernelGGL(ids_exact_kernel, grid, dim3(64), 0, s, ev_begin, ev_end, 0, a, vox,
-                          reinterpret_cast<uint2*>(ids), depth);
-  else
-    hipLaunchKernelGGL(ids_exact_kernel, grid, dim3(64), 0, s, a, vox, reinterpret_cast<uint2*>(ids), depth);
+  launch_kernel(ids_exact_kernel, grid, dim3(64), 0, s, ev_begin, ev_end, a, vox, reinterpret_cast<uint2*>(ids), depth);
 }
 
-void launch_reproject(const KArgs& a, const ReprojArgs& r, hipStream_t s, hipEvent_t ev_begin, hipEvent_t ev_end) {
+void launch_reproject(const KArgs& a, const ReprojArgs& r, int32_t fetch, uint8_t* taps, hipStream_t s,
+                      hipEvent_t ev_begin, hipEvent_t ev_end) {
   const dim3 grid(uint32_t(a.width + 15) / 16u, uint32_t(a.rows + 15) / 16u);
-  if (ev_begin || ev_end)
-    hipExtLaunchKernelGGL(reproject_kernel, grid, dim3(kReprojWg), 0, s, ev_begin, ev_end, 0, a, r);
+  if (fetch == VRT_FETCH_NEAREST && !taps)
+    launch_kernel(reproject_kernel, grid, dim3(kReprojWg), 0, s, ev_begin, ev_end, a, r);
   else
-    hipLaunchKernelGGL(reproject_kernel, grid, dim3(kReprojWg), 0, s, a, r);
-}
-
-void launch_reproject_fetch(const KArgs& a, const ReprojArgs& r, int32_t fetch, uint8_t* taps, hipStream_t s,
-                            hipEvent_t ev_begin, hipEvent_t ev_end) {
-  if (fetch == VRT_FETCH_NEAREST && !taps) return launch_reproject(a, r, s, ev_begin, ev_end);
-  auto kern = fetch == VRT_FETCH_BILINEAR ? reproject_bilinear_kernel : reproject_nearest_taps_kernel;
-  const dim3 grid(uint32_t(a.width + 15) / 16u, uint32_t(a.rows + 15) / 16u);
-  if (ev_begin || ev_end)
-    hipExtLaunchKernelGGL(kern, grid, dim3(kReprojWg), 0, s, ev_begin, ev_end, 0, a, r, taps);
-  else
-    hipLaunchKernelGGL(kern, grid, dim3(kReprojWg), 0, s, a, r, taps);
+    launch_kernel(fetch == VRT_FETCH_BILINEAR ? reproject_bilinear_kernel : reproject_nearest_taps_kernel, grid,
+                  dim3(kReprojWg), 0, s, ev_begin, ev_end, a, r, taps);
 }
 
 void launch_spatial(const SpatialArgs& a, hipStream_t s, hipEvent_t ev_begin, hipEvent_t ev_end) {
@@ -994,153 +978,62 @@ void launch_spatial(const SpatialArgs& a, hipStream_t s, hipEvent_t ev_begin, hi
               : a.step == 2             ? spatial_lds_kernel<2>
                                         : spatial_lds_kernel<4>;
   const dim3 grid(uint32_t(a.width + 15) / 16u, uint32_t(a.rows + 15) / 16u);
-  if (ev_begin || ev_end)
-    hipExtLaunchKernelGGL(kern, grid, dim3(kSpatialWg), 0, s, ev_begin, ev_end, 0, a);
-  else
-    hipLaunchKernelGGL(kern, grid, dim3(kSpatialWg), 0, s, a);
+  launch_kernel(kern, grid, dim3(kSpatialWg), 0, s, ev_begin, ev_end, a);
 }
 
 void launch_reduce_counters(unsigned long long* rep, unsigned long long* dst, hipStream_t s) {
-  hipLaunchKernelGGL(reduce_counters_kernel, dim3(1), dim3(64), 0, s, rep, dst);
+  launch_kernel(reduce_counters_kernel, dim3(1), dim3(64), 0, s, nullptr, nullptr, rep, dst);
 }
 
-// ---- the skip field (upload, vrt_update_volume_region): the boxes of a regional rebuild ------------
-namespace {
-
-struct Span {  // cells [a, b] of one axis, clipped to the volume
-  int32_t a, b;
-};
-Span clip_span(int64_t a, int64_t b, int32_t n) {
-  return Span{int32_t(std::max<int64_t>(a, 0)), int32_t(std::min<int64_t>(b, int64_t(n) - 1))};
-}
-// Edit cells [lo, hi) of an axis. An occupied cell kFwdCap or more cells ahead cannot lower a capped
-// F, so the anchors whose F can change lie up to kFwdCap - 1 cells behind the edit (against sg) ...
-Span fwd_anchors(int32_t lo, int32_t hi, int sg, int32_t n) {
-  const int64_t r = int64_t(kFwdCap) - 1;
-  return sg > 0 ? clip_span(lo - r, int64_t(hi) - 1, n) : clip_span(lo, int64_t(hi) - 1 + r, n);
-}
-// ... a pass over them reads its input up to kFwdCap - 1 cells ahead (the same cells for both signs) ...
-Span fwd_inputs(int32_t lo, int32_t hi, int32_t n) {
-  const int64_t r = int64_t(kFwdCap) - 1;
-  return clip_span(lo - r, int64_t(hi) - 1 + r, n);
-}
-// ... and G(w) = F(w - s) - 1 moves them one cell ahead: the packed texels (with the edit's own
-// cells, for the voxel bytes)
-Span fwd_texels(int32_t lo, int32_t hi, int sg, int32_t n) {
-  const int64_t r = int64_t(kFwdCap) - 1;
-  const int64_t a = (sg > 0 ? lo - r : int64_t(lo)) + sg, b = (sg > 0 ? int64_t(hi) - 1 : int64_t(hi) - 1 + r) + sg;
-  return clip_span(std::min<int64_t>(a, lo), std::max<int64_t>(b, int64_t(hi) - 1), n);
-}
-// the centred D (single layout): cells within `reach` of the edit
-Span dist_span(int32_t lo, int32_t hi, int64_t reach, int32_t n) {
-  return clip_span(lo - reach, int64_t(hi) - 1 + reach, n);
-}
-Region region_of(Span x, Span y, Span z) {
-  return Region{x.a, y.a, z.a, x.b - x.a + 1, y.b - y.a + 1, z.b - z.a + 1};
-}
-
-}  // namespace
-
-int volume_edit_plan(int32_t n, int octants, const int32_t lo[3], const int32_t ext[3], int32_t* out) {
-  for (int o = 0; o < octants; ++o)
-    for (int a = 0; a < 3; ++a) {
-      const int32_t hi = lo[a] + ext[a];
-      const Span t = octants == 8 ? fwd_texels(lo[a], hi, (o >> a & 1) ? -1 : 1, n)
-                                  : dist_span(lo[a], hi, int64_t(kDistCap) - 1, n);
-      out[o * 6 + a] = t.a;
-      out[o * 6 + 3 + a] = t.b + 1;
-    }
-  return octants;
-}
+// ---- the skip field (upload, vrt_update_volume_region) ---------------------------------------------
 
 void launch_edit_apply(const uint8_t* box, uint8_t* vox, uint32_t n, const int32_t lo[3], const int32_t ext[3],
                        unsigned long long* counts, hipStream_t s) {
   const Region b{lo[0], lo[1], lo[2], ext[0], ext[1], ext[2]};
-  hipLaunchKernelGGL(edit_apply_kernel, dim3(grid_blocks(region_cells(b))), dim3(256), 0, s, box, vox, b, n,
-                     counts);
+  launch_cells(edit_apply_kernel, region_cells(b), s, box, vox, b, n, counts);
 }
 
+// The passes of skipfield_passes (vrt_skipfield_plan.cpp: every box is chosen there) in its order, one launch
+// each. The scratch thirds are N^3 bytes each: every box is clipped to the volume, so each fits one.
 void launch_volume_edit_passes(const uint8_t* vox, uint8_t* tmp, uint16_t* packed, uint32_t n, int octants,
                                const int32_t lo[3], const int32_t ext[3], bool distances, hipStream_t s) {
-  const int32_t ni = int32_t(n);
-  const int32_t hi[3] = {lo[0] + ext[0], lo[1] + ext[1], lo[2] + ext[2]};
   const uint64_t vol = uint64_t(n) * n * n, pvol = uint64_t(n + 1) * (n + 1) * (n + 1);
-  const Region box{lo[0], lo[1], lo[2], ext[0], ext[1], ext[2]};
-  const Region whole{0, 0, 0, ni, ni, ni};
-  // region-local scratch: every box is clipped to the volume, so each fits N^3 bytes. For an upload
-  // (lo = 0, ext = N on every axis) every span clips to [0, N - 1] and every box below is `whole`.
-  uint8_t* da = tmp;
-  uint8_t* db = tmp + vol;
-  if (octants == 8) {
-    // octant forward distances: 2 x passes, 4 y passes, 8 z passes + packs (x -> y -> z nesting)
-    uint8_t* dc = tmp + 2 * vol;
-    const Span iy = fwd_inputs(lo[1], hi[1], ni), iz = fwd_inputs(lo[2], hi[2], ni);
-    for (int sx = 1; sx >= -1; sx -= 2) {
-      const Span ax = fwd_anchors(lo[0], hi[0], sx, ni);
-      const Region rx = region_of(ax, iy, iz);  // x pass: the y and z passes' inputs
-      if (distances)
-        hipLaunchKernelGGL(fwd_pass_kernel, dim3(grid_blocks(region_cells(rx))), dim3(256), 0, s, vox,
-                           whole, da, rx, n, 0, sx, 1);
-      for (int sy = 1; sy >= -1; sy -= 2) {
-        const Span ay = fwd_anchors(lo[1], hi[1], sy, ni);
-        const Region ry = region_of(ax, ay, iz);
-        if (distances)
-          hipLaunchKernelGGL(fwd_pass_kernel, dim3(grid_blocks(region_cells(ry))), dim3(256), 0, s, da,
-                             rx, db, ry, n, 1, sy, 0);
-        for (int sz = 1; sz >= -1; sz -= 2) {
-          const Span az = fwd_anchors(lo[2], hi[2], sz, ni);
-          const Region rz = region_of(ax, ay, az);
-          const int o = (sx < 0 ? 1 : 0) | (sy < 0 ? 2 : 0) | (sz < 0 ? 4 : 0);
-          uint16_t* dst = packed + size_t(o) * pvol;
-          if (distances) {
-            hipLaunchKernelGGL(fwd_pass_kernel, dim3(grid_blocks(region_cells(rz))), dim3(256), 0, s, db,
-                               ry, dc, rz, n, 2, sz, 0);
-            const Region pb = region_of(fwd_texels(lo[0], hi[0], sx, ni), fwd_texels(lo[1], hi[1], sy, ni),
-                                        fwd_texels(lo[2], hi[2], sz, ni));
-            hipLaunchKernelGGL(fwd_pack_kernel, dim3(grid_blocks(region_cells(pb))), dim3(256), 0, s, vox,
-                               dc, rz, dst, pb, n, sx, sy, sz);
-          } else {
-            hipLaunchKernelGGL(fwd_pack_kernel, dim3(grid_blocks(region_cells(box))), dim3(256), 0, s, vox,
-                               static_cast<const uint8_t*>(nullptr), box, dst, box, n, sx, sy, sz);
-          }
-        }
+  const SkipPlan plan = skipfield_passes(int32_t(n), octants, lo, ext, distances);
+  for (int i = 0; i < plan.count; ++i) {
+    const SkipPass& p = plan.pass[i];
+    // the distances read: the canonical volume (a first pass), a scratch third, or none (a pack that keeps them)
+    const uint8_t* src = p.first ? vox : (p.src >= 0 ? tmp + uint64_t(p.src) * vol : nullptr);
+    uint8_t* dst = p.dst >= 0 ? tmp + uint64_t(p.dst) * vol : nullptr;
+    switch (p.kind) {
+      case SkipPassKind::kFwdPass:
+        launch_cells(fwd_pass_kernel, region_cells(p.out), s, src, p.in, dst, p.out, n, p.axis, p.sg[p.axis], p.first);
+        break;
+      case SkipPassKind::kFwdPack:
+        launch_cells(fwd_pack_kernel, region_cells(p.out), s, vox, src, p.in, packed + size_t(p.octant) * pvol, p.out,
+                     n, p.sg[0], p.sg[1], p.sg[2]);
+        break;
+      case SkipPassKind::kDistPass:
+        launch_cells(dist_pass_kernel, region_cells(p.out), s, src, p.in, dst, p.out, n, p.axis, p.first);
+        break;
+      case SkipPassKind::kVolumePack:
+        launch_cells(pack_volume_kernel, region_cells(p.out), s, vox, src, p.in, packed, p.out, n);
+        break;
+      case SkipPassKind::kEdgePack: {
+        const EdgeSlabs e = edge_slabs(p.out, p.wrap);
+        launch_cells(edge_pack_kernel, e.cz + e.cy + e.cx, s, vox, packed, pvol, octants, p.out, p.wrap, n);
+        break;
       }
     }
-  } else if (distances) {
-    const int64_t r1 = int64_t(kDistCap) - 1;
-    const Span ax = dist_span(lo[0], hi[0], r1, ni), ay = dist_span(lo[1], hi[1], r1, ni);
-    const Span az = dist_span(lo[2], hi[2], r1, ni);
-    // the z pass reads y-pass values kDistCap - 1 cells to both sides in z, the y pass x-pass values in y
-    const Span iy = dist_span(lo[1], hi[1], 2 * r1, ni), iz = dist_span(lo[2], hi[2], 2 * r1, ni);
-    const Region rx = region_of(ax, iy, iz), ry = region_of(ax, ay, iz), rz = region_of(ax, ay, az);
-    hipLaunchKernelGGL(dist_pass_kernel, dim3(grid_blocks(region_cells(rx))), dim3(256), 0, s, vox, whole,
-                       da, rx, n, 0, 1);
-    hipLaunchKernelGGL(dist_pass_kernel, dim3(grid_blocks(region_cells(ry))), dim3(256), 0, s, da, rx, db,
-                       ry, n, 1, 0);
-    hipLaunchKernelGGL(dist_pass_kernel, dim3(grid_blocks(region_cells(rz))), dim3(256), 0, s, db, ry, da,
-                       rz, n, 2, 0);
-    hipLaunchKernelGGL(pack_volume_kernel, dim3(grid_blocks(region_cells(rz))), dim3(256), 0, s, vox, da,
-                       rz, packed, rz, n);
-  } else {
-    hipLaunchKernelGGL(pack_volume_kernel, dim3(grid_blocks(region_cells(box))), dim3(256), 0, s, vox,
-                       static_cast<const uint8_t*>(nullptr), box, packed, box, n);
-  }
-  // texel N of an axis repeats voxel 0: rewritten when the box holds coordinate 0 of that axis
-  const int wrap = (lo[0] == 0 ? 1 : 0) | (lo[1] == 0 ? 2 : 0) | (lo[2] == 0 ? 4 : 0);
-  if (wrap) {
-    const EdgeSlabs e = edge_slabs(box, wrap);
-    hipLaunchKernelGGL(edge_pack_kernel, dim3(grid_blocks(e.cz + e.cy + e.cx)), dim3(256), 0, s, vox, packed, pvol,
-                       octants, box, wrap, n);
   }
 }
 
 void launch_glass_share(const uint8_t* vox, uint64_t total, unsigned long long* out, hipStream_t s) {
-  hipLaunchKernelGGL(glass_share_kernel, dim3(grid_blocks(total)), dim3(256), 0, s, vox, total, out);
+  launch_cells(glass_share_kernel, total, s, vox, total, out);
 }
 
 void launch_build_scene(uint8_t* vox, int scene, uint32_t n, const float* noise, hipStream_t s) {
   const uint64_t vol = uint64_t(n) * n * n;
-  hipLaunchKernelGGL(build_scene_kernel, dim3(grid_blocks(vol)), dim3(256), 0, s, vox, scene, n, noise);
+  launch_cells(build_scene_kernel, vol, s, vox, scene, n, noise);
 }
 
 void launch_assemble_blocks(const uint32_t* bands, uint64_t band_words, int32_t k, int32_t sh, int32_t width,
@@ -1148,27 +1041,22 @@ void launch_assemble_blocks(const uint32_t* bands, uint64_t band_words, int32_t 
   if (height <= 0 || width <= 0) return;
   const bool vec = width % 4 == 0 && band_words % 4 == 0 && frame_pitch % 4 == 0 &&
                    (reinterpret_cast<uintptr_t>(bands) & 15u) == 0 && (reinterpret_cast<uintptr_t>(frame) & 15u) == 0;
-  if (vec)
-    hipLaunchKernelGGL(assemble_blocks_kernel<true>, dim3(uint32_t(height)), dim3(256), 0, s, bands, band_words, k,
-                       sh, width, frame, frame_pitch);
-  else
-    hipLaunchKernelGGL(assemble_blocks_kernel<false>, dim3(uint32_t(height)), dim3(256), 0, s, bands, band_words, k,
-                       sh, width, frame, frame_pitch);
+  launch_kernel(vec ? assemble_blocks_kernel<true> : assemble_blocks_kernel<false>, dim3(uint32_t(height)), dim3(256), 0,
+                s, nullptr, nullptr, bands, band_words, k, sh, width, frame, frame_pitch);
 }
 
 void launch_pack_rgb8(const uint32_t* rgba, uint64_t pixels, uint8_t* rgb, hipStream_t s) {
   const uint64_t quads = pixels / 4u;
   if (quads == 0) return;
-  hipLaunchKernelGGL(pack_rgb8_kernel, dim3(grid_blocks(quads)), dim3(256), 0, s, reinterpret_cast<const uint4*>(rgba), quads,
-                     reinterpret_cast<uint32_t*>(rgb));
+  launch_cells(pack_rgb8_kernel, quads, s, reinterpret_cast<const uint4*>(rgba), quads, reinterpret_cast<uint32_t*>(rgb));
 }
 
 void launch_assemble_blocks_rgb8(const uint8_t* bands, uint64_t band_px, int32_t k, int32_t sh, int32_t width,
                                  int32_t height, uint32_t* frame, uint64_t frame_pitch, hipStream_t s) {
   if (height <= 0 || width <= 0) return;
-  hipLaunchKernelGGL(assemble_blocks_rgb8_kernel, dim3(uint32_t(height)), dim3(256), 0, s,
-                     reinterpret_cast<const uint32_t*>(bands), band_px, k, sh, width, reinterpret_cast<uint4*>(frame),
-                     frame_pitch);
+  launch_kernel(assemble_blocks_rgb8_kernel, dim3(uint32_t(height)), dim3(256), 0, s, nullptr, nullptr,
+                reinterpret_cast<const uint32_t*>(bands), band_px, k, sh, width, reinterpret_cast<uint4*>(frame),
+                frame_pitch);
 }
 
 int run_fast_math_check(unsigned long long* host_out) {
@@ -1178,7 +1066,7 @@ int run_fast_math_check(unsigned long long* host_out) {
   hipError_t e = hipMemcpy(d, init, sizeof(init), hipMemcpyHostToDevice);
   if (e == hipSuccess) {
     // 2^32 patterns: 2^24 threads of 256 patterns each
-    hipLaunchKernelGGL(fast_math_check_kernel, dim3(1u << 16), dim3(256), 0, nullptr, d);
+    launch_kernel(fast_math_check_kernel, dim3(1u << 16), dim3(256), 0, nullptr, nullptr, nullptr, d);
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipMemcpy(host_out, d, sizeof(init), hipMemcpyDeviceToHost);
@@ -1188,8 +1076,8 @@ int run_fast_math_check(unsigned long long* host_out) {
 
 void launch_randomize(const float* dir, const float* pos, int n, float randomness, float seed,
                       float* out, hipStream_t s) {
-  hipLaunchKernelGGL(randomize_kernel, dim3((n + 63) / 64), dim3(64), 0, s, dir, pos, n,
-                     randomness, seed, out);
+  launch_kernel(randomize_kernel, dim3((n + 63) / 64), dim3(64), 0, s, nullptr, nullptr, dir, pos, n, randomness, seed,
+                out);
 }
 
 }  // namespace vrt

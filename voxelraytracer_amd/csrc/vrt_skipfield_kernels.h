@@ -5,20 +5,19 @@
 // region-local scratch (x fastest inside the box), and the outside-distance terms use the global
 // coordinate, so a pass over a box yields exactly the bytes a pass over the volume has on that box.
 // An upload is the edit of the box [0, N)^3: every box is then the whole volume.
-// Includes vrt_internal.h, vrt_math.h and vrt_walk.h (kDistCap, the packed texel layout).
+// Includes vrt_internal.h, vrt_math.h and vrt_walk.h (kDistCap, the packed texel layout), and
+// vrt_skipfield_plan.h (Region, and the host arithmetic that chooses every box the kernels are given).
 #ifndef VRT_SKIPFIELD_KERNELS_H
 #define VRT_SKIPFIELD_KERNELS_H
 
 #include "vrt_internal.h"
 #include "vrt_math.h"
+#include "vrt_skipfield_plan.h"
 #include "vrt_walk.h"
 
 namespace vrt {
 
-// A box of voxels: origin and extent in global coordinates (every extent >= 1, inside [0, N)^3).
-struct Region {
-  int32_t x0, y0, z0, ex, ey, ez;
-};
+static_assert(kPlanDistCap == kDistCap, "the pass plan's boxes are sized by the kernels' cap");
 
 // Cells are counted in 32 bits. The largest box is the whole volume at N = 1024 (single layout):
 // 2^30 cells. A grid-stride counter ends its loop below cells + gridDim * 256 <= 2^30 + 16384 * 256
