@@ -308,6 +308,17 @@ int vrt_debug_randomize(vrt_ctx* ctx, const float* dir, const float* pos, int32_
  * Synchronous. */
 int vrt_debug_fast_math(vrt_ctx* ctx, uint64_t* out);
 
+/* Added within v15 (detect by symbol lookup). Diagnostic: the two power forms the certified pass relies
+ * on, over all 2^32 float bit patterns x on the context's first device. out[6]:
+ * (a) the skybox's sun disc 10 * pow(x, 400) by the library's log2 and exp2: out[0] = patterns x in
+ *     [-0, 0.75] (the sign bit alone, or 0 <= x <= 0.75), out[1] = those among them whose result is not +0,
+ *     out[2] = patterns with x < 0 or NaN, out[3] = those among them whose result is no NaN;
+ * (b) the specular power pow(max(x, 0), 10) by the library's forms and by the bare hardware log and exp:
+ *     out[4] = patterns whose two results differ in their bits while either is at least 2^-100 in magnitude
+ *     (or a NaN), out[5] = the first such pattern (~0 if none).
+ * out[1], out[3] and out[4] must be 0. Synchronous. */
+int vrt_debug_pow_forms(vrt_ctx* ctx, uint64_t* out);
+
 /* Diagnostic (test rehearsal of the multi-GPU path on a one-GPU box): a one-device context takes
  * the k-device path through RCCL with a one-rank communicator (ncclCommInitAll over its device):
  * the volume upload goes through ncclBroadcast (in place) and vrt_render_frame_device through

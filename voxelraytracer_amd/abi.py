@@ -253,6 +253,8 @@ SIGNATURES = {
     "vrt_debug_packed_volume": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
     "vrt_debug_collectives": (C.c_int, [C.c_void_p]),
     "vrt_debug_fast_math": (C.c_int, [C.c_void_p, C.c_void_p]),
+    # added within v15 (detect by symbol lookup): the proof run of the certified pass's power forms
+    "vrt_debug_pow_forms": (C.c_int, [C.c_void_p, C.c_void_p]),
     "vrt_volume_octants": (C.c_int, [C.c_void_p]),
     "vrt_set_skip_layout": (C.c_int, [C.c_void_p, C.c_int32]),
     "vrt_set_certified": (C.c_int, [C.c_void_p, C.c_int32]),

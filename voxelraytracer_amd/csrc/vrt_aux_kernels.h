@@ -198,6 +198,44 @@ __global__ void fast_math_check_kernel(unsigned long long* out) {
   atomicAdd(&out[6], (unsigned long long)sq_bad);
 }
 
+// Diagnostic (vrt_debug_pow_forms): every float bit pattern x through the two powers the certified pass
+// shortens. out: {(a) patterns in [-0, 0.75], those whose 10 * gpow(x, 400) (apply_sky_color's sun disc) is not
+// +0, patterns with x < 0 or NaN, those whose result is no NaN; (b) patterns whose gpow and gpow_raw of
+// (max(x, 0), 10) (cert_shade_hit's specular power) differ in their bits while either is a NaN or at least
+// 2^-100 in magnitude, the first such pattern (or ~0)}. The values pass through opaque registers, so that the
+// compiler evaluates each form as the render kernels do and folds nothing across the comparison.
+__global__ void pow_forms_check_kernel(unsigned long long* out) {
+  const uint64_t per = 256;
+  const uint64_t base = (uint64_t(blockIdx.x) * blockDim.x + threadIdx.x) * per;
+  uint32_t far = 0, far_bad = 0, neg = 0, neg_bad = 0, spec_bad = 0;
+  for (uint64_t i = 0; i < per; ++i) {
+    const uint32_t u = uint32_t(base + i);
+    float x = __uint_as_float(u);
+    asm volatile("" : "+v"(x));
+    const float sun = 10.0f * gpow(x, 400.0f);
+    if (u == 0x80000000u || (x >= 0.0f && x <= 0.75f)) {
+      ++far;
+      if (__float_as_uint(sun) != 0u) ++far_bad;
+    } else if (!(x >= 0.0f)) {  // x < 0 or NaN (-0 was taken above)
+      ++neg;
+      if (sun == sun) ++neg_bad;
+    }
+    float m = gmax(x, 0.0f);
+    asm volatile("" : "+v"(m));
+    const float lib = gpow(m, 10.0f), raw = gpow_raw(m, 10.0f);
+    const bool tiny = __builtin_fabsf(lib) < 0x1p-100f && __builtin_fabsf(raw) < 0x1p-100f;  // (false for a NaN)
+    if (__float_as_uint(lib) != __float_as_uint(raw) && !tiny) {
+      ++spec_bad;
+      atomicMin(&out[5], (unsigned long long)u);
+    }
+  }
+  atomicAdd(&out[0], (unsigned long long)far);
+  atomicAdd(&out[1], (unsigned long long)far_bad);
+  atomicAdd(&out[2], (unsigned long long)neg);
+  atomicAdd(&out[3], (unsigned long long)neg_bad);
+  atomicAdd(&out[4], (unsigned long long)spec_bad);
+}
+
 }  // namespace vrt
 
 #endif  // VRT_AUX_KERNELS_H

@@ -651,7 +651,15 @@ __device__ __forceinline__ bool cert_shade_hit(const Ctx& c, const Ray& ray, con
       const float rd = ((a == 0 ? -px : px) + (a == 1 ? -py : py)) + (a == 2 ? -pz : pz);
       const uint32_t m = mat_id(h.byte);
       const float diffuse = mat_kd(m) * gmax(ns, 0.0f);
-      const float specular = mat_ks(m, TEX) * gpow(gmax(rd, 0.0f), mat_exp(m, TEX));
+      // Colour-only: the power by the bare log and exp (gpow_raw). Where the two forms differ both are below
+      // 2^-100, and 0.2 * 2^-100 is far below half an ulp of kAmbient + diffuse >= 0.3 (2^-26): the sum below
+      // has the same bits, and nothing else reads the specular term.
+      float pw;
+      if constexpr (!TEX && kCutSpec)
+        pw = gpow_raw(gmax(rd, 0.0f), mat_exp(m, TEX));
+      else
+        pw = gpow(gmax(rd, 0.0f), mat_exp(m, TEX));
+      const float specular = mat_ks(m, TEX) * pw;
       lit = kAmbient + diffuse + specular;
     } else {
       lit = lit_generic();
@@ -1424,7 +1432,7 @@ __device__ __forceinline__ bool cert_pixel(const Ctx& c0, const Ray& ray0, f3& c
   f3 color = mk(0.0f, 0.0f, 0.0f);
   if (h.res == CERT_MISS) {
     CERT_DIAG(2);
-    if (!(LEAN && PHASE_STOP(6))) apply_sky_color(c, ray0, color);
+    if (!(LEAN && PHASE_STOP(6))) apply_sky_color<LEAN && kCutSky>(c, ray0, color);
     color_out = color;
     return true;
   }

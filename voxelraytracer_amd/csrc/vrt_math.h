@@ -88,6 +88,13 @@ __device__ __forceinline__ float gsign(float x) { return x > 0.0f ? 1.0f : (x < 
 __device__ __forceinline__ float gmin(float x, float y) { return y < x ? y : x; }
 __device__ __forceinline__ float gmax(float x, float y) { return __builtin_fmaxf(x, y); }
 __device__ __forceinline__ float gpow(float x, float y) { return exp2f(y * log2f(x)); }
+// The same by the bare v_log_f32 and v_exp_f32, without the library forms' denormal scaling (a compare, a
+// select and a multiply or an add around each): the two differ only where x or the result is denormal, and
+// there both are below 2^-100 for the specular exponent 10 (exhaustive over x >= 0: vrt_debug_pow_forms,
+// tests/test_gpu_pow_forms.py). For a caller that adds the power to a term of ordinary size only.
+__device__ __forceinline__ float gpow_raw(float x, float y) {
+  return __builtin_amdgcn_exp2f(y * __builtin_amdgcn_logf(x));
+}
 __device__ __forceinline__ float mixf(float x, float y, float a) { return x * (1.0f - a) + y * a; }
 __device__ __forceinline__ f3 reflect3(f3 i, f3 n) {
   const float s = 2.0f * dot3(n, i);

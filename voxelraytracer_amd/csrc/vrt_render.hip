@@ -1074,6 +1074,21 @@ int run_fast_math_check(unsigned long long* host_out) {
   return e == hipSuccess ? VRT_OK : VRT_ERR_DEVICE;
 }
 
+int run_pow_forms_check(unsigned long long* host_out) {
+  unsigned long long* d = nullptr;
+  if (hipMalloc(&d, 6 * sizeof(unsigned long long)) != hipSuccess) return VRT_ERR_OOM;
+  const unsigned long long init[6] = {0, 0, 0, 0, 0, ~0ull};
+  hipError_t e = hipMemcpy(d, init, sizeof(init), hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    // 2^32 patterns: 2^24 threads of 256 patterns each
+    launch_kernel(pow_forms_check_kernel, dim3(1u << 16), dim3(256), 0, nullptr, nullptr, nullptr, d);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpy(host_out, d, sizeof(init), hipMemcpyDeviceToHost);
+  (void)hipFree(d);
+  return e == hipSuccess ? VRT_OK : VRT_ERR_DEVICE;
+}
+
 void launch_randomize(const float* dir, const float* pos, int n, float randomness, float seed,
                       float* out, hipStream_t s) {
   launch_kernel(randomize_kernel, dim3((n + 63) / 64), dim3(64), 0, s, nullptr, nullptr, dir, pos, n, randomness, seed,

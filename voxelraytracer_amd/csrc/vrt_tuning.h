@@ -14,7 +14,7 @@
      defined(VRT_ORD_DIV) || defined(VRT_ORD_MIN_ROUNDS) || defined(VRT_DEFER_GRID_DIV) ||                      \
      defined(VRT_DEFER_GRID_DIV_COLOR) || defined(VRT_QUERY_WG_WAVES) || defined(VRT_TRACE_WG_WAVES) ||         \
      defined(VRT_TRACE_MIN_WAVES) || defined(VRT_DEFER_LDS_PAD) || defined(VRT_EXACT_VGPRS) ||                  \
-     defined(VRT_SPATIAL_LDS_STEPS)) &&                                                                        \
+     defined(VRT_SPATIAL_LDS_STEPS) || defined(VRT_NO_SKY_ZERO) || defined(VRT_NO_RAW_SPECULAR)) &&            \
     !defined(VRT_DIAGNOSTIC_BUILD)
 #error "the VRT_* tuning values are A/B knobs of make variant builds (make variant NAME=... DEFS=-DVRT_...=...)"
 #endif
@@ -209,6 +209,22 @@ constexpr int kTraceMinWaves = VRT_TRACE_MIN_WAVES;
 // 0.0468 and 0.0469 in the two processes, at step 16 0.0528 and 0.0527 (profiles/spatial_bench.txt)
 constexpr uint32_t kSpatialLdsSteps = VRT_SPATIAL_LDS_STEPS;
 static_assert((kSpatialLdsSteps & ~0x16u) == 0, "only steps 1, 2 and 4 have an LDS-staged form");
+
+// The once-per-pixel cuts of the certified pass's DEFER instances (r16), each switched off by a
+// define of its own in a diagnostic build (make variant NAME=nosky DEFS=-DVRT_NO_SKY_ZERO), for the per-cut
+// counter table (profiles/r16_ndc_sky/flag_cuts.txt). Images are identical with either of them off.
+//  - kCutSky: a primary miss's sun disc without log and exp where no missing lane of the wave is near the sun;
+//  - kCutSpec: the specular power of a colour-only primary hit by the bare v_log_f32 / v_exp_f32.
+#ifdef VRT_NO_SKY_ZERO
+constexpr bool kCutSky = false;
+#else
+constexpr bool kCutSky = true;
+#endif
+#ifdef VRT_NO_RAW_SPECULAR
+constexpr bool kCutSpec = false;
+#else
+constexpr bool kCutSpec = true;
+#endif
 
 }  // namespace vrt
 

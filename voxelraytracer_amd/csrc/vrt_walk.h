@@ -731,9 +731,22 @@ __device__ __forceinline__ void apply_hit_color(const Ctx& c, const Hit& h, floa
 }
 
 // GetSkyboxColor (:386-393), then the second mix at :420
+// FAR (the certified pass's primary misses, cert_pixel<LEAN>): the sun disc without its log and exp where no
+// lane of the wave that is here looks within 41 degrees of the sun (a ballot: the branch is wave-uniform).
+// With d = dot(sun, u): for d in [-0, 0.75] the power is +0 (400 log2(0.75) = -166 is far below the smallest
+// denormal's exponent; log2(+-0) = -inf), and 10 * +0 = +0; for d < 0 or NaN it is NaN, which both gmax below
+// drop, whatever its payload (their other operands are no NaN: u is a certified ray's direction). Exhaustive
+// over d: vrt_debug_pow_forms, tests/test_gpu_pow_forms.py. The power itself keeps the library's forms: near
+// the sun its denormal results reach the float frame.
+template <bool FAR = false>
 __device__ __forceinline__ void apply_sky_color(const Ctx& c, const Ray& ray, f3& color) {
   const f3 u = normalize3(ray.dir);
-  const float sun = 10.0f * gpow(dot3(c.sun_n, u), 400.0f);
+  const float d = dot3(c.sun_n, u);
+  float sun;
+  if (FAR && __ballot(d > 0.75f) == 0ull)
+    sun = d >= 0.0f ? 0.0f : __builtin_nanf("");
+  else
+    sun = 10.0f * gpow(d, 400.0f);
   const float grad = (u.y + 1.0f) * 0.5f;
   const float sy = c.sky_sy;  // gmax(u_SunDir.y, 0), precomputed (a wave-uniform constant)
   const f3 sk = mk(gmax(0.0f, sun) * sy, gmax(grad * 0.75f, sun) * sy, gmax(grad, 0.0f) * sy);
