@@ -19,7 +19,8 @@ HDR := include/vrt.h $(CSRC)/vrt_internal.h $(CSRC)/vrt_context.h $(CSRC)/vrt_ba
        $(CSRC)/vrt_instances.h $(CSRC)/vrt_skipfield_plan.h \
        $(CSRC)/vrt_tuning.h $(CSRC)/vrt_diag.h $(CSRC)/vrt_math.h \
        $(CSRC)/vrt_walk.h $(CSRC)/vrt_cert.h $(CSRC)/vrt_aux_kernels.h \
-       $(CSRC)/vrt_skipfield_kernels.h $(CSRC)/vrt_query_kernels.h $(CSRC)/vrt_trace_kernels.h \
+       $(CSRC)/vrt_skipfield_kernels.h $(CSRC)/vrt_query_kernels.h $(CSRC)/vrt_cert_debug_kernels.h \
+       $(CSRC)/vrt_trace_kernels.h \
        $(CSRC)/vrt_ids_kernels.h $(CSRC)/vrt_reproject_kernels.h $(CSRC)/vrt_spatial_kernels.h
 # RCCL: volume broadcast and the frame gather of multi-device contexts (vrt_volume.cpp, vrt_frames.cpp)
 LIBS := -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib

@@ -298,6 +298,18 @@ int vrt_set_cert_trees(vrt_ctx* ctx, int32_t on);
 int vrt_debug_randomize(vrt_ctx* ctx, const float* dir, const float* pos, int32_t n,
                         float randomness, float seed, float* out);
 
+/* Added within v15 (detect by symbol lookup). Diagnostic: one certified walk per listed ray
+ * on the resident volume, which must have the eight-octant skip layout (vrt_volume_octants() == 8).
+ * rays: `count` (<= 2^24) records of 32 bytes, vrt_ray's layout with the reserved word read as float len0,
+ * the ray's length so far (0 <= len0 <= 1e4, |max_length| <= 1e4), origins in volume coordinates.
+ * kind: 0 the walk of a ray in air from an exact origin, 1 the shadow walk along the ray's own direction,
+ * 2 and 3 the same two walks in the certified pass's form (its unguarded loads). out: `count` records of
+ * 32 bytes: int32 res (0 a certified miss, 1 a certified hit, 2 unsure, 3 not started: the ray's
+ * direction, start cell or start layers do not allow a certified walk), uint32 byte, int32 axis, int32 cell
+ * x, y, z of the hit, float u, the hit's parameter along the ray, and float eu, the bound of the exact
+ * walk's parameter error there (byte to eu mean something for res 1). Host pointers. Synchronous. */
+int vrt_debug_cert_walks(vrt_ctx* ctx, const void* rays, int64_t count, int32_t kind, void* out);
+
 /* Diagnostic: the kernels' fast correctly rounded reciprocal (the hardware reciprocal plus one
  * Newton step) and square root (the hardware square root plus its residual fix) checked against
  * the IEEE division and square root over all 2^32 float bit patterns on the context's first

@@ -77,6 +77,8 @@ def lib():
         L.oracle_trace_pixel.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                          C.c_void_p, C.c_int, C.c_void_p]
         L.oracle_trace_pixel.restype = C.c_int
+        L.oracle_march_rays.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
+        L.oracle_march_rays.restype = C.c_int
         _lib = L
     return _lib
 
@@ -137,6 +139,26 @@ def march_one(vox: np.ndarray, n: int, pos, dir, max_len: float = 100.0):
                                    C.byref(steps))
     return dict(found=bool(found), vidx=vidx.value, len=ln.value, point=pt, normal=nm,
                 steps=steps.value)
+
+
+# oracle_march_rays' records: 8 floats in, 16 words out
+RAY_LEN0_DTYPE = np.dtype([("origin", "<f4", (3,)), ("max_length", "<f4"), ("dir", "<f4", (3,)), ("len0", "<f4")])
+MARCH_DTYPE = np.dtype([("found", "<i4"), ("voxel", "<i4"), ("index", "<i4"), ("vidx", "<i4"), ("len", "<f4"),
+                        ("point", "<f4", (3,)), ("normal", "<f4", (3,)), ("steps", "<u4"), ("flags", "<u4"),
+                        ("pad", "<u4", (3,))])
+
+
+def march_rays(vox: np.ndarray, n: int, rays: np.ndarray, shadow: bool = False) -> np.ndarray:
+    """RayMarch (shadow: RayMarchShadow, `found` then the blocked bit) of every ray of a RAY_LEN0_DTYPE
+    list in air, each with its own max_length and start length len0 -> MARCH_DTYPE records."""
+    vox = np.ascontiguousarray(vox, np.uint8)
+    rays = np.ascontiguousarray(rays)
+    assert rays.dtype.itemsize == 32 and vox.size == n * n * n, (rays.dtype, vox.size, n)
+    out = np.zeros(len(rays), MARCH_DTYPE)
+    rc = lib().oracle_march_rays(vox.ctypes.data, n, rays.ctypes.data, len(rays), int(shadow), out.ctypes.data)
+    if rc != 0:
+        raise ValueError(f"oracle_march_rays rc={rc}")
+    return out
 
 
 def render(cam: Camera, vox: np.ndarray, n: int, params: Params, row0: int = 0, rows=None,

@@ -650,6 +650,56 @@ EXPORT int oracle_march_one(const uint8_t* vox, int n, const float pos[3], const
   return h.found;
 }
 
+/* RayMarch (kind 0) or RayMarchShadow (kind 1) of `count` listed rays in air, each with its own limit and
+ * start length: a ray is 8 floats {origin, max_length, dir, len0} (vrt_ray's layout, the reserved word read
+ * as the ray's length so far). out: 16 words per ray: found (kind 1: blocked), voxel, index, vidx as int32,
+ * len, point[3], normal[3] as float, steps, flags as uint32, three zero words; a miss and a shadow march
+ * leave the hit's fields zero (vidx -1). Rays are independent: an OpenMP loop where the build has OpenMP. */
+EXPORT int oracle_march_rays(const uint8_t* vox, int n, const float* rays, int64_t count, int kind,
+                             uint32_t* out) {
+  if (!vox || n <= 0 || count < 0 || (count > 0 && (!rays || !out)) || (kind != 0 && kind != 1))
+    return VRT_ERR_INVALID;
+#ifdef _OPENMP
+#pragma omp parallel for schedule(dynamic, 256)
+#endif
+  for (int64_t i = 0; i < count; i++) {
+    const float* q = rays + 8 * i;
+    ctx_t c;
+    memset(&c, 0, sizeof c);
+    c.vox = vox;
+    c.n = n;
+    c.fn = (float)n;
+    c.max_len = q[3];
+    c.sun = mk(0.0f, 1.0f, 0.0f);
+    cnt_t k;
+    memset(&k, 0, sizeof k);
+    ray_t r;
+    memset(&r, 0, sizeof r);
+    r.pos = mk(q[0], q[1], q[2]);
+    r.dir = mk(q[4], q[5], q[6]);
+    r.len = q[7];
+    r.energy = 1.0f;
+    uint32_t steps = 0, flags = 0;
+    uint32_t* o = out + 16 * i;
+    memset(o, 0, 16 * sizeof(uint32_t));
+    if (kind == 1) {
+      o[0] = (uint32_t)march_shadow(&c, &r, &k, &steps, &flags);
+      o[3] = (uint32_t)-1;
+    } else {
+      const isect_t h = march(&c, &r, &k, &steps, &flags);
+      const float f[7] = {h.len, h.point.x, h.point.y, h.point.z, h.normal.x, h.normal.y, h.normal.z};
+      o[0] = (uint32_t)h.found;
+      o[1] = h.voxel;
+      o[2] = (uint32_t)h.index;
+      o[3] = (uint32_t)(h.found ? h.vidx : -1);
+      memcpy(o + 4, f, sizeof f);
+    }
+    o[11] = steps;
+    o[12] = flags;
+  }
+  return VRT_OK;
+}
+
 EXPORT void oracle_refract(const float i[3], const float nrm[3], float eta, float out[3]) {
   v3 r = refract(mk(i[0], i[1], i[2]), mk(nrm[0], nrm[1], nrm[2]), eta);
   out[0] = r.x; out[1] = r.y; out[2] = r.z;

@@ -204,7 +204,7 @@ static cres_t cwalk(v3 P, v3 D, float U, int shadow, const int* cell0, double e0
         if (gam[b] > mg) mg = gam[b];
       }
       r.exitc = (double)s1 - mback < 2.0 * mg ? X_LEN_TIE : X_LEN_MISS;
-      r.res = C_MISS;
+      r.res = r.exitc == X_LEN_TIE ? C_UNC : C_MISS;
       return r;
     }
     int nc[3] = {cell[0], cell[1], cell[2]};
@@ -214,22 +214,37 @@ static cres_t cwalk(v3 P, v3 D, float U, int shadow, const int* cell0, double e0
       if (b == a) continue;
       if ((double)sig[b] - s1 < gam[a] + gam[b]) { ah[b] = 1; nah++; }
       float q = sig[b] - arcp[b];
-      if (q >= 0.0f && (double)s1 - q < gam[a] + gam[b]) { bh[b] = 1; nbh++; }
+      /* a plane behind counts down to -gam_b, not 0 (the kernel's bhx / bhy / bhz): a ray that starts
+       * on a plane has it at parameter 0 up to rounding */
+      if ((double)q > -gam[b] && (double)s1 - q < gam[a] + gam[b]) { bh[b] = 1; nbh++; }
     }
     const int ev = is_event(path_byte(nc), shadow);
     if (ev) {
       if (shadow && (nah || nbh) && nah + nbh < 2) {
-        /* blocked whichever order the exact walk takes: near-behind b still samples nc (or
-         * nc - e_b first); near-ahead b samples nc, or cell + e_b and then nc + e_b */
+        /* Blocked whichever order the exact walk takes (nc blocks: the order a, b samples it):
+         *  - near-ahead b: crossed first, the walk samples cell + e_b and then, in a second step, nc +
+         *    e_b; tied with a, it samples nc + e_b alone. So nc + e_b must block (a blocking cell + e_b
+         *    with a clear nc + e_b is lit in the tie), and the second step must happen: the walk's len
+         *    before it, the crossing of b at up to s1 + gam_a + gam_b, must be below the limit;
+         *  - near-behind b: the walk still samples nc, at once or after nc - e_b, in a second step whose
+         *    len before is the crossing of a at up to s1 + gam_a: the same length condition.
+         * tg = gam_a + max gam bounds both, so s1 + tg + gL < U (it implies prev + gL < U). */
         int ok = 1;
+        double mg = gam[0] > gam[1] ? gam[0] : gam[1];
+        if (gam[2] > mg) mg = gam[2];
+        const double tg = gam[a] + mg;
         for (int b = 0; b < 3; b++) {
           if (!ah[b]) continue;
-          int c1[3] = {cell[0], cell[1], cell[2]}, c2[3] = {nc[0], nc[1], nc[2]};
-          c1[b] += s[b];
+          int c2[3] = {nc[0], nc[1], nc[2]};
           c2[b] += s[b];
-          if (!is_event(alt_byte(c1), 1) && !is_event(alt_byte(c2), 1)) ok = 0;
+          /* as a cell of the volume (path_byte): with index N on axis b the tie's sample lies half a cell
+           * beyond the volume's face and reads nothing, and the order b, a ends at TestCube unless the
+           * coordinate is N exactly; the wrapped plane 0 (alt_byte) is what the walk may read, not must */
+          if (!is_event(path_byte(c2), 1)) ok = 0;
         }
-        if (ok && (double)prev + gL < (double)U) { r.res = C_HIT; r.byte = path_byte(nc); r.axis = a; r.exitc = X_HIT_ONE_FLAG; return r; }
+        if (ok && (double)prev + gL < (double)U && (double)s1 + tg + gL < (double)U) {
+          r.res = C_HIT; r.byte = path_byte(nc); r.axis = a; r.exitc = X_HIT_ONE_FLAG; return r;
+        }
       }
       if (nah || nbh) { r.res = C_UNC; r.why = 2; r.exitc = X_EVENT_FLAGS; return r; }
       if ((double)prev + gL >= (double)U) { r.res = C_UNC; r.why = 3; r.exitc = X_EVENT_LEN; return r; }
@@ -435,4 +450,89 @@ EXPORT void cs_run(const float* inv_pv, int w, int h, const float* sun, float ma
   for (int q = 0; q < 32; q++) out[q] = acc[q];
   out[30] = wu / (tw * th);
   out[31] = wup / (tw * th);
+}
+
+/* ---- one certified walk per listed ray (tests/test_cert_rays.py, tests/test_gpu_cert_rays.py) ----
+ * The model's side of the kernel's debug hook vrt_debug_cert_walks: a ray is 8 floats {origin, max_length,
+ * dir, len0} (vrt_ray's layout with the reserved word read as len0). The start is the kernel's
+ * (cert_secondary, cert_shadow_exact; csrc/vrt_cert.h): fast_path_ok, exact_start_cell and
+ * start_layers_clear restated here; a ray one of them refuses is "not started" (C_NOSTART). Then cwalk
+ * from the exact walk's own start cell with U = max_length - len0, len0b = len0, no uncertain origin. */
+enum { C_NOSTART = 3 };
+
+/* exact_start_cell: the exact walk's start cell, inside the volume, its first planes the cell's */
+static int start_cell(const float p[3], const float d[3], int cell[3]) {
+  for (int a = 0; a < 3; a++) {
+    const int up = d[a] > 0.0f;
+    const float fc = up ? floorf(p[a]) : ceilf(p[a]) - 1.0f;
+    if (!(fc >= 0.0f && fc < (float)N)) return 0;
+    cell[a] = (int)fc;
+    const float wp = up ? floorf(p[a] + 1.0f) : ceilf(p[a] - 1.0f);
+    if (wp != (float)(cell[a] + up)) return 0;
+  }
+  return 1;
+}
+
+/* start_layers_clear: the cells of layer k the exact walk samples while a start coordinate P_a = k
+ * (D_a < 0) has not rounded off the plane (float arithmetic, as the kernel's) */
+static int layers_clear(const float p[3], const float d[3], const int cell[3], int shadow) {
+  for (int a = 0; a < 3; a++) {
+    if (!(d[a] < 0.0f) || p[a] != floorf(p[a])) continue;
+    const float off = (0x1p-22f * fmaxf(fabsf(p[a]), 1.0f) + 1e-5f) / fabsf(d[a]);
+    if (off >= 1.0f) return 0;
+    int q[3] = {cell[0], cell[1], cell[2]};
+    q[a] += 1;
+    int early[3] = {0, 0, 0};
+    for (int b = 0; b < 3; b++) {
+      if (b == a) continue;
+      const float plane = (float)(cell[b] + (d[b] > 0.0f ? 1 : 0));
+      early[b] = (plane - p[b]) / d[b] < off;
+    }
+    const int b1 = a == 0 ? 1 : 0, b2 = a == 2 ? 1 : 2;
+    const int s1 = d[b1] > 0.0f ? 1 : -1, s2 = d[b2] > 0.0f ? 1 : -1;
+    if (shadow && (early[b1] || early[b2])) return 0;
+    int r[3];
+    if (early[b1]) {
+      r[0] = q[0]; r[1] = q[1]; r[2] = q[2]; r[b1] += s1;
+      if (is_event(alt_byte(r), shadow)) return 0;
+    }
+    if (early[b2]) {
+      r[0] = q[0]; r[1] = q[1]; r[2] = q[2]; r[b2] += s2;
+      if (is_event(alt_byte(r), shadow)) return 0;
+    }
+    if (early[b1] && early[b2]) {
+      r[0] = q[0]; r[1] = q[1]; r[2] = q[2]; r[b1] += s1; r[b2] += s2;
+      if (is_event(alt_byte(r), shadow)) return 0;
+    }
+  }
+  return 1;
+}
+
+/* out: 6 words per ray: res (C_MISS / C_HIT / C_UNC / C_NOSTART), byte, axis, exitc (X_*) as int32, u, eu
+ * as float. kind 0: air walk, 1: shadow walk. cs_build first. */
+EXPORT void cs_walk_rays(const float* rays, long count, int kind, int32_t* out) {
+  GSCALE = 1.0;
+  MARGIN = 1.0f / 64.0f;
+#pragma omp parallel for schedule(dynamic, 256)
+  for (long i = 0; i < count; i++) {
+    const float* q = rays + 8 * i;
+    const float p[3] = {q[0], q[1], q[2]}, d[3] = {q[4], q[5], q[6]};
+    const float max_len = q[3], len0 = q[7];
+    int32_t* o = out + 6 * i;
+    memset(o, 0, 6 * sizeof(int32_t));
+    int ok = len0 >= 0.0f && len0 <= 1.0e4f && fabsf(max_len) <= 1.0e4f, cell[3];
+    for (int a = 0; a < 3; a++) ok = ok && fabsf(d[a]) >= 0x1p-64f && fabsf(d[a]) <= 1.0e4f;
+    if (!ok || !start_cell(p, d, cell) || !layers_clear(p, d, cell, kind)) {
+      o[0] = C_NOSTART;
+      continue;
+    }
+    const cres_t r = cwalk(mk(p[0], p[1], p[2]), mk(d[0], d[1], d[2]), max_len - len0, kind, NULL, 0.0,
+                           (double[3]){0, 0, 0}, (double)len0);
+    o[0] = r.res;
+    o[1] = r.byte;
+    o[2] = r.axis;
+    o[3] = r.exitc;
+    memcpy(&o[4], &r.u, 4);
+    memcpy(&o[5], &r.eu, 4);
+  }
 }

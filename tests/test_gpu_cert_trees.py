@@ -182,16 +182,17 @@ def test_lattice_camera_sample(built, scene, n):
                 assert bad.size == 0, (pos, rot, (R, T), trees, ep, bad[:3].tolist())
 
 
-@pytest.mark.xfail(strict=True, reason="known, unfixed (DESIGN.md §10, HISTORY r06_s38-s39): the certified "
-                   "shadow walk from these exact hit points disagrees with the exact shadow walk")
 @pytest.mark.parametrize("scene,n,pos,rot,R,T", [
     ("refraction", 128, (-29.0, -44.5, 21.5), (-89.99, 225.0, 0.0), 1, 2),
     ("terrain", 64, (-21.0, 1.0, 16.0), (90.0, 0.0, 0.0), 4, 4),
 ])
 def test_certified_shadow_open_cases(built, scene, n, pos, rot, R, T):
-    """The two cameras of the 72 000-frame lattice stress (r06_s38) that still differ, in one or two
+    """The two cameras of the 72 000-frame lattice stress (r06_s38) that differed, in one or two
     pixels, in every certified mode including exact primaries with certified shadows (set_certified
-    0 on these glass-light volumes keeps certified shadow walks from exact hit points)."""
+    0 on these glass-light volumes keeps certified shadow walks from exact hit points), until the
+    shadow walk's one-flag hit was corrected (DESIGN.md §6 "Certified walks, ray by ray": the tie,
+    the plane's copy and the second step's length; tests/test_gpu_cert_rays.py). Each camera was a
+    strict expected failure until then; both render bit-identically now."""
     w, h = 320, 180
     with vrt.Renderer(0) as r:
         r.upload_volume(vrt.build_scene(scene, n), n)

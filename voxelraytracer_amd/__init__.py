@@ -793,6 +793,18 @@ class Renderer:
         return out
 
 
+    def debug_cert_walks(self, rays: np.ndarray, kind: int) -> np.ndarray:
+        """One certified walk per ray of `rays` (abi.CERT_RAY_DTYPE records) on the resident volume
+        (vrt_debug_cert_walks), for tests -> abi.CERT_WALK_DTYPE records. kind 0: the air walk, 1: the
+        shadow walk along the ray's direction, 2 and 3: the same in the certified pass's form."""
+        r = np.ascontiguousarray(rays)
+        if r.dtype.itemsize != 32 or r.ndim != 1:
+            raise ValueError("debug_cert_walks: a one-dimensional array of 32-byte ray records")
+        out = np.zeros(len(r), dtype=abi.CERT_WALK_DTYPE)
+        self._check(self._lib.vrt_debug_cert_walks(self._h, r.ctypes.data, len(r), kind, out.ctypes.data),
+                    "vrt_debug_cert_walks")
+        return out
+
     def comm_join(self, ids, nranks: int, rank: int):
         """vrt_comm_join: one RCCL communicator per id (a list of VRT_COMM_ID_BYTES-byte ids), this
         context's device as `rank` of `nranks` (blocks until every rank joined each one)."""

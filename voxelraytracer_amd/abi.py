@@ -123,6 +123,10 @@ class RayHit(C.Structure):
 # numpy dtypes of one vrt_ray and one vrt_ray_hit record (the latter starts with a vrt_hit)
 RAY_DTYPE = [("origin", "<f4", (3,)), ("max_length", "<f4"), ("dir", "<f4", (3,)), ("reserved", "<u4")]
 RAY_HIT_DTYPE = HIT_DTYPE + [("point", "<f4", (3,)), ("face", "<u4")]
+# vrt_debug_cert_walks: a vrt_ray with the reserved word read as len0, and the walk's result
+CERT_RAY_DTYPE = [("origin", "<f4", (3,)), ("max_length", "<f4"), ("dir", "<f4", (3,)), ("len0", "<f4")]
+CERT_WALK_DTYPE = [("res", "<i4"), ("byte", "<u4"), ("axis", "<i4"), ("cell", "<i4", (3,)), ("u", "<f4"), ("eu", "<f4")]
+CERT_MISS, CERT_HIT, CERT_UNSURE, CERT_NOT_STARTED = 0, 1, 2, 3
 
 
 # shaded ray queries (vrt_trace_rays*, vrt_trace_pixels)
@@ -330,6 +334,8 @@ SIGNATURES = {
     "vrt_upload_atlas": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
     "vrt_debug_randomize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float,
                                       C.c_float, C.c_void_p]),
+    # added within v15 (detect by symbol lookup): certified walks for a ray list
+    "vrt_debug_cert_walks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
     "vrt_terrain_noise": (C.c_int, [C.c_int32, C.c_uint32, C.c_void_p]),
     "vrt_build_scene": (C.c_int, [C.c_int32, C.c_int32, C.c_uint32, C.c_void_p]),
     "vrt_camera_make": (

@@ -411,14 +411,24 @@ __device__ __forceinline__ CertResult cert_walk(const Ctx& c, const f3 P, const 
           if (nf != 0u && ev) {
             // an event with flags: unsure, but for a shadow walk's one-flag hit
             res = CERT_UNSURE;
-            if (SHADOW && lenok && __builtin_popcount(nf) == 1) {
-              // blocked whichever way the exact walk goes: near-behind b still samples nc (or nc - e_b
-              // first); near-ahead b samples nc, or cell + e_b and then nc + e_b
+            // Blocked whichever way the exact walk goes (nc blocks: the order a, b samples it first):
+            //  - near-ahead b: crossed first, the walk samples cell + e_b and then, in a second step, nc +
+            //    e_b; tied with a, it samples nc + e_b alone. So nc + e_b must block: a blocking cell + e_b
+            //    with a clear nc + e_b is lit in the tie. And it must block as a cell of the volume
+            //    (path_texel, not alt_byte's wrapped plane N): with index N on axis b the tie's sample lies
+            //    half a cell beyond the volume's face and reads nothing, and the order b, a ends at TestCube
+            //    unless the coordinate is N exactly: the plane's copy is what the walk may read, not must;
+            //  - near-behind b: the walk samples nc at once, or nc - e_b and then nc in a second step;
+            //  - either second step happens only if the walk's len before it is below the limit: the other
+            //    crossing's parameter, within gam_a + gam_b <= tg of s1. lenok (prev + gL < U) speaks of the
+            //    step at s1 alone, so the block asks s1 + tg + gL < U.
+            // (The ray tests found the tie, the plane's copy and the second step's length as shadow rays the
+            // walk called blocked and the exact walk ends lit: tests/test_cert_rays.py)
+            if (SHADOW && lenok && __builtin_popcount(nf) == 1 && s1 + tg + gL < U) {
               bool ok = true;
               if (nf & 7u) {
                 const int bx = (nf & 1u) ? sx : 0, by = (nf & 2u) ? sy : 0, bz = (nf & 4u) ? sz : 0;
-                ok = cert_event<true>(alt_byte(c, cx + bx, cy + by, cz + bz, obase), 0u) ||
-                     cert_event<true>(alt_byte(c, nx + bx, ny + by, nz + bz, obase), 0u);
+                ok = cert_event<true>(path_texel(c, nx + bx, ny + by, nz + bz, obase) & kVoxMask, 0u);
               }
               if (ok) res = CERT_HIT;
             }

@@ -367,6 +367,39 @@ int vrt_debug_randomize(vrt_ctx* ctx, const float* dir, const float* pos, int32_
   return VRT_OK;
 }
 
+int vrt_debug_cert_walks(vrt_ctx* ctx, const void* rays, int64_t count, int32_t kind, void* out) {
+  if (!ctx) return VRT_ERR_INVALID;
+  const Shard& s = ctx->sh[0];
+  if (!s.d_vox_pad) return fail(ctx, VRT_ERR_NO_VOLUME, "no volume uploaded");
+  if (s.octants != 8) return fail(ctx, VRT_ERR_UNSUPPORTED, "certified walks need the eight-octant skip layout");
+  if (kind < 0 || kind > 3) return fail(ctx, VRT_ERR_INVALID, "walk kind must be 0, 1, 2 or 3");
+  if (count < 0 || count > (int64_t(1) << 24)) return fail(ctx, VRT_ERR_INVALID, "ray count must be in [0, 2^24]");
+  if (count == 0) return VRT_OK;
+  if (!rays || !out) return fail(ctx, VRT_ERR_INVALID, "null ray or result buffer");
+  DeviceGuard guard;
+  VRT_HIP(ctx, hipSetDevice(s.device));
+  const size_t bytes = size_t(count) * 32u;  // a ray and a result are 32 bytes each
+  void *d_in = nullptr, *d_out = nullptr;
+  if (hipMalloc(&d_in, bytes) != hipSuccess || hipMalloc(&d_out, bytes) != hipSuccess) {
+    (void)hipFree(d_in);
+    return fail(ctx, VRT_ERR_OOM, "hipMalloc");
+  }
+  hipError_t e = hipMemcpy(d_in, rays, bytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    vrt::KArgs a{};  // the kernel reads the volume's fields only
+    a.n = s.n;
+    a.fn = float(s.n);
+    a.ostride = octant_stride(s);
+    vrt::launch_cert_walks_debug(a, kind, s.d_vox_pad, d_in, uint32_t(count), d_out, nullptr);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpy(out, d_out, bytes, hipMemcpyDeviceToHost);
+  (void)hipFree(d_in);
+  (void)hipFree(d_out);
+  if (e != hipSuccess) return hip_fail(ctx, e, "vrt_debug_cert_walks");
+  return VRT_OK;
+}
+
 int vrt_debug_collectives(vrt_ctx* ctx) {
   if (!ctx) return VRT_ERR_INVALID;
   if (ctx->sh.size() != 1 || !ctx->comms.empty())

@@ -165,6 +165,11 @@ void launch_ray_query(const KArgs& a, int32_t kind, const uint16_t* vox, const v
 constexpr int32_t kTraceRays = 0, kTracePixels = 1;
 void launch_ray_trace(const KArgs& a, int32_t kind, const uint16_t* vox, const void* in, uint32_t count,
                       vrt_ray_color* out, hipStream_t s, hipEvent_t ev_begin = nullptr, hipEvent_t ev_end = nullptr);
+// cert_walks_debug_kernel (vrt_cert_debug_kernels.h; vrt_debug_cert_walks): `count` (>= 1) 32-byte ray records
+// of `in`, one per lane, through the certified walk `kind` (0..3) into 32-byte result records; only a.n, a.fn
+// and a.ostride are read. The volume must be the eight-octant layout (the certified walks' skip field).
+void launch_cert_walks_debug(const KArgs& a, int32_t kind, const uint16_t* vox, const void* in, uint32_t count,
+                             void* out, hipStream_t s);
 // ids_exact_kernel (vrt_ids_kernels.h): rows [a.row0, a.row0 + a.rows) of the frame `a` describes (make_args
 // with row_step 1; a.pitch pixels between rows of ids / depth; depth may be null), one launch, an 8x8 tile per
 // one-wave workgroup. ev_begin / ev_end: optional device timestamps, as launch_render's

@@ -849,6 +849,8 @@ __global__ void __launch_bounds__(64, exact_cap_waves(kExactVgprs))
 
 // the ray-query kernel (vrt_cast_rays*, vrt_pick_pixels): here because it calls init_ctx and primary_ray
 #include "vrt_query_kernels.h"
+// certified walks for a ray list (vrt_debug_cert_walks): here because it calls init_ctx
+#include "vrt_cert_debug_kernels.h"
 // the shaded ray-query kernels (vrt_trace_rays*, vrt_trace_pixels): after exact_pixel, which they call
 #include "vrt_trace_kernels.h"
 // the ID and depth pass (vrt_render_ids*): after primary_ray and the ray-query kernel's ray_hit_face
@@ -944,6 +946,14 @@ void launch_ray_query(const KArgs& a, int32_t kind, const uint16_t* vox, const v
   // one lane per query: ceil(count / kQueryWg) workgroups (count <= 2^30)
   const dim3 grid((count + uint32_t(kQueryWg) - 1u) / uint32_t(kQueryWg));
   launch_kernel(kern, grid, dim3(kQueryWg), 0, s, ev_begin, ev_end, a, vox, in, count, reinterpret_cast<uint4*>(hits));
+}
+
+void launch_cert_walks_debug(const KArgs& a, int32_t kind, const uint16_t* vox, const void* in, uint32_t count,
+                             void* out, hipStream_t s) {
+  // one lane per ray: ceil(count / kCertDebugWg) workgroups
+  const dim3 grid((count + uint32_t(kCertDebugWg) - 1u) / uint32_t(kCertDebugWg));
+  launch_kernel(cert_walks_debug_kernel, grid, dim3(kCertDebugWg), 0, s, nullptr, nullptr, a, vox,
+                static_cast<const float4*>(in), count, kind, static_cast<uint4*>(out));
 }
 
 void launch_ray_trace(const KArgs& a, int32_t kind, const uint16_t* vox, const void* in, uint32_t count,
