@@ -487,11 +487,13 @@ int vrt_trace_pixels(vrt_ctx* ctx, const vrt_camera* cam, const vrt_params* para
 /* What the frame SHOWS, per pixel and without shading: the voxel and the face the pixel's primary ray
  * meets, and the hit's depth. An ID buffer outlines a selection, an edited box or the voxels under the
  * cursor without a pick per pixel; a depth buffer composites rasterised gizmos, particles or UI against
- * the ray-traced frame; face and voxel byte per pixel guide an edge-aware filter. Every pixel is walked by
- * the pick's exact march, an 8x8 tile per wave, in one kernel launch: the price of vrt_pick_pixels over
- * every pixel without its pixel list, its 32-byte records and its host staging (DESIGN.md §6 "ID and depth
- * pass"; a certified-walk kernel for octant layouts is not part of the library yet). The pass runs on the
- * context's first device. */
+ * the ray-traced frame; face and voxel byte per pixel guide an edge-aware filter. By default every pixel is
+ * walked by the pick's exact march, an 8x8 tile per wave, in one kernel launch: the price of vrt_pick_pixels
+ * over every pixel without its pixel list, its 32-byte records and its host staging. With
+ * vrt_set_ids_certified(1) on an octant layout the launch is the certified ID kernel instead: the same tiles,
+ * each pixel by the certified walk, and a pixel that walk cannot settle by the exact march in its own lane of
+ * the same kernel; the records and depths are the same bytes (DESIGN.md §6 "ID and depth pass"). The pass
+ * runs on the context's first device. */
 
 /* 8 bytes. voxel_index and face are vrt_ray_hit's fields of the same names for the pixel's primary ray
  * (a miss: voxel_index = -1, face = 0). */
@@ -530,10 +532,24 @@ int vrt_render_ids_async(vrt_ctx* ctx, const vrt_camera* cam, const vrt_params* 
 int vrt_render_ids(vrt_ctx* ctx, const vrt_camera* cam, const vrt_params* params, vrt_pixel_id* ids,
                    float* depth);
 
-/* Of the last synchronous vrt_render_ids: pixels rendered, and how many of them took the exact kernel:
- * all of them, on every layout, while the library has no certified ID kernel. Zeros before the first such
- * call. */
+/* Of the last synchronous vrt_render_ids: pixels rendered, and how many of them were walked by the exact
+ * march: all of them when the exact ID kernel ran (mode 0, or the single layout); with the certified ID
+ * kernel, the pixels its walk left to the exact march in their lanes (counted through a context-owned device
+ * word that only the synchronous call zeroes, passes and reads back). Zeros before the first such call. */
 int vrt_ids_deferred(vrt_ctx* ctx, uint64_t* pixels, uint64_t* deferred);
+
+/* The ID pass's kernel (added within v15: detect by symbol lookup). mode 0 (the default): the exact ID kernel
+ * for every pixel. mode 1: the certified ID kernel where the resident volume has the eight-octant skip layout
+ * (vrt_volume_octants() == 8); on the single layout (N = 1024, vrt_set_skip_layout(1)) the exact kernel still
+ * runs. One kernel and one launch either way: a pixel whose certified walk is unsure, or whose start the
+ * walk's checks refuse, is walked exactly in its own lane, so vrt_render_ids_async keeps its contract (no
+ * allocation, no memset, no atomics, no context-owned state, capturable) and vrt_render_ids,
+ * vrt_render_ids_async and vrt_render_frame_reprojected return the same bytes in both modes. The mode
+ * survives uploads. VRT_ERR_INVALID for any other mode (nothing changes) or a null context. */
+int vrt_set_ids_certified(vrt_ctx* ctx, int32_t mode);
+
+/* 1 when the next ID pass will launch the certified ID kernel (mode 1 and an octant layout resident), else 0. */
+int vrt_ids_certified(const vrt_ctx* ctx);
 
 /* ---- reprojected temporal filter (added within v15: detect by symbol lookup) ----------------- */
 /* A temporal filter whose history follows the camera: the first consumer of the ID and depth pass. The
@@ -591,8 +607,8 @@ int vrt_reproject_temporal_async(vrt_ctx* ctx, const vrt_camera* cam, const vrt_
  * stats (optional): kernel_ms is the GPU time from the first launch's start to the last launch's end;
  * counters (VRT_STATS_COUNTERS) are VRT_ERR_UNSUPPORTED.
  * Limits: the default fetch is nearest, so a history that is resampled frame after frame drifts by up to
- * half a pixel per frame (vrt_set_reprojected_fetch selects the bilinear fetch); the exact ID pass runs inside
- * every call. */
+ * half a pixel per frame (vrt_set_reprojected_fetch selects the bilinear fetch); the ID pass runs inside
+ * every call (the exact ID kernel, or the certified one after vrt_set_ids_certified(1): the same bytes). */
 int vrt_render_frame_reprojected(vrt_ctx* ctx, const vrt_camera* cam, const vrt_params* params, float alpha,
                                  uint8_t* out_rgba8, vrt_stats* stats);
 

@@ -476,10 +476,21 @@ class Renderer:
 
     def ids_deferred(self):
         """vrt_ids_deferred: (pixels, deferred) of the last render_ids: how many pixels it rendered and
-        how many of them took the exact kernel (all of them: there is no certified ID kernel yet)."""
+        how many of them the exact march walked: all of them when the exact ID kernel ran, and with the
+        certified ID kernel (set_ids_certified(1) on an octant layout) those its walk could not settle."""
         px, de = C.c_uint64(), C.c_uint64()
         self._check(self._lib.vrt_ids_deferred(self._h, C.byref(px), C.byref(de)), "vrt_ids_deferred")
         return int(px.value), int(de.value)
+
+    def set_ids_certified(self, mode: int):
+        """vrt_set_ids_certified: the ID pass's kernel. 0 (the default): the exact ID kernel for every pixel;
+        1: the certified ID kernel on an octant layout (certified walks, the exact march in the lane of a
+        pixel they cannot settle). One launch either way; IDs and depths are the same bytes."""
+        self._check(self._lib.vrt_set_ids_certified(self._h, int(mode)), "vrt_set_ids_certified")
+
+    def ids_certified(self) -> int:
+        """vrt_ids_certified: 1 when the next ID pass launches the certified ID kernel, else 0."""
+        return int(self._lib.vrt_ids_certified(self._h))
 
     def reproject_temporal_async(self, cam: Camera, params: Params, prev_pv, alpha: float, row0: int, rows: int,
                                  pitch: int, d_raw: int, d_ids: int, d_depth: int, d_prev: int, d_prev_ids: int,

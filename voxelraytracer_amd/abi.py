@@ -181,7 +181,9 @@ ADDED_IN = {"vrt_render_temporal_batch_async": 14, "vrt_set_cert_trees": 15,
             # added within v15 after the reprojected filter (bilinear history fetch)
             "vrt_reproject_temporal_fetch_async": 16, "vrt_set_reprojected_fetch": 16,
             # added within v15 after the bilinear fetch (ID-guided spatial filter)
-            "vrt_spatial_filter_async": 16, "vrt_spatial_filter": 16, "vrt_set_reprojected_spatial": 16}
+            "vrt_spatial_filter_async": 16, "vrt_spatial_filter": 16, "vrt_set_reprojected_spatial": 16,
+            # added within v15 after the spatial filter (certified ID kernel)
+            "vrt_set_ids_certified": 16, "vrt_ids_certified": 16}
 
 SIGNATURES = {
     "vrt_abi_version": (C.c_int, []),
@@ -231,6 +233,9 @@ SIGNATURES = {
                                        C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vrt_render_ids": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.c_void_p, C.c_void_p]),
     "vrt_ids_deferred": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    # added within v15 (detect by symbol lookup): certified ID kernel
+    "vrt_set_ids_certified": (C.c_int, [C.c_void_p, C.c_int32]),
+    "vrt_ids_certified": (C.c_int, [C.c_void_p]),
     # added within v15 (detect by symbol lookup): reprojected temporal filter
     "vrt_camera_forward": (C.c_int, [C.POINTER(Camera), C.c_void_p]),
     "vrt_reproject_temporal_async": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.c_void_p,

@@ -203,10 +203,15 @@ struct vrt_ctx {
   vrt::Stage<vrt_ray> d_query_in;
   vrt::Stage<vrt_ray_hit> d_query_out;
   // first device: staging of the synchronous ID and depth pass (vrt_render_ids): records and depths,
-  // grown to the largest frame. ids_pixels / ids_deferred: of the last such call (vrt_ids_deferred)
+  // grown to the largest frame. ids_pixels / ids_deferred: of the last such call (vrt_ids_deferred).
+  // d_ids_count: one word, allocated with the staging: the certified ID kernel's exact-path pixels of a
+  // synchronous call (zeroed on the main stream before the launch, copied back with the frame; the
+  // capturable entry point never passes it). ids_cert_req: vrt_set_ids_certified
   vrt::Stage<vrt_pixel_id> d_ids_stage;
   vrt::Stage<float> d_depth_stage;
+  vrt::Stage<uint32_t> d_ids_count;
   uint64_t ids_pixels = 0, ids_deferred = 0;
+  int32_t ids_cert_req = 0;
   // first device: vrt_render_frame_reprojected's staging for frames of rp_w x rp_h (grown to the largest frame):
   // the raw frame, the depth, ping-pong filtered frames and noise-free ID buffers (rp_cur: the last call's),
   // the last call's forward matrix, and whether the next call has a history (rp_valid). Separate from
@@ -314,10 +319,13 @@ int ensure_stage(vrt_ctx* ctx, size_t bytes);
 // checked (the kernels' 8- and 4-byte stores)
 int check_ids(vrt_ctx* ctx, const vrt_camera* cam, const vrt_params* p, int32_t row0, int32_t rows, int64_t pitch,
               const void* ids, const void* depth, bool device);
-// One ID pass over rows [row0, row0 + rows) (rows >= 1) on `st`: one launch of the exact ID kernel, no
-// allocation, no host synchronisation
+// One ID pass over rows [row0, row0 + rows) (rows >= 1) on `st`: one launch, of the certified ID kernel where
+// ids_certified() holds (vrt_set_ids_certified(1) and an octant layout resident), else of the exact ID kernel;
+// no allocation, no host synchronisation. d_n_exact (null unless the synchronous vrt_render_ids counts): the
+// certified kernel adds its exact-path pixels to that device word; the exact kernel does not touch it
+bool ids_certified(const vrt_ctx* ctx);
 int enqueue_ids(vrt_ctx* ctx, const vrt_camera* cam, const vrt_params* p, int32_t row0, int32_t rows, int32_t pitch,
-                vrt_pixel_id* d_ids, float* d_depth, hipStream_t st);
+                vrt_pixel_id* d_ids, float* d_depth, hipStream_t st, uint32_t* d_n_exact = nullptr);
 
 }  // namespace vrt
 

@@ -172,9 +172,12 @@ void launch_cert_walks_debug(const KArgs& a, int32_t kind, const uint16_t* vox, 
                              void* out, hipStream_t s);
 // ids_exact_kernel (vrt_ids_kernels.h): rows [a.row0, a.row0 + a.rows) of the frame `a` describes (make_args
 // with row_step 1; a.pitch pixels between rows of ids / depth; depth may be null), one launch, an 8x8 tile per
-// one-wave workgroup. ev_begin / ev_end: optional device timestamps, as launch_render's
+// one-wave workgroup. ev_begin / ev_end: optional device timestamps, as launch_render's. certified: the same
+// grid of ids_cert_kernel instead (the volume must be the eight-octant layout, the certified walk's skip field):
+// still one launch; n_exact (certified only, may be null): a device word the launch adds its exact-path pixels to
 void launch_render_ids(const KArgs& a, const uint16_t* vox, vrt_pixel_id* ids, float* depth, hipStream_t s,
-                       hipEvent_t ev_begin = nullptr, hipEvent_t ev_end = nullptr);
+                       hipEvent_t ev_begin = nullptr, hipEvent_t ev_end = nullptr, bool certified = false,
+                       uint32_t* n_exact = nullptr);
 // reproject_kernel and its two other fetch forms (vrt_reproject_kernels.h): the band `a` describes (make_args with row_step 1, as
 // launch_render_ids; a.pitch pixels between band rows of raw, ids, depth, out and src), one launch, a 16x16
 // tile per workgroup of kReprojWg threads. prev / prev_ids: the whole previous frame, prev_pitch pixels

@@ -21,15 +21,22 @@ int vrt::check_ids(vrt_ctx* ctx, const vrt_camera* cam, const vrt_params* p, int
   return VRT_OK;
 }
 
+// Whether the next ID pass launches the certified ID kernel: asked for, and the resident volume has the
+// eight-octant skip layout its walk needs (the single layout, N = 1024 or vrt_set_skip_layout(1): the exact kernel)
+bool vrt::ids_certified(const vrt_ctx* ctx) {
+  const Shard& s = ctx->sh[0];
+  return ctx->ids_cert_req == 1 && s.d_vox_pad && s.octants == 8;
+}
+
 int vrt::enqueue_ids(vrt_ctx* ctx, const vrt_camera* cam, const vrt_params* p, int32_t row0, int32_t rows,
-                     int32_t pitch, vrt_pixel_id* d_ids, float* d_depth, hipStream_t st) {
+                     int32_t pitch, vrt_pixel_id* d_ids, float* d_depth, hipStream_t st, uint32_t* d_n_exact) {
   Shard& s = ctx->sh[0];
   // the frame's argument block, as the frame launches fill it (launch): primary_ray reads it
   vrt::KArgs a = make_args(ctx, s, cam, p, row0, rows, 1);
   a.pitch = pitch;
   hipEvent_t eb, ee;
   launch_timing_events(ctx, eb, ee);
-  vrt::launch_render_ids(a, s.d_vox_pad, d_ids, d_depth, st, eb, ee);
+  vrt::launch_render_ids(a, s.d_vox_pad, d_ids, d_depth, st, eb, ee, ids_certified(ctx), d_n_exact);
   VRT_HIP(ctx, hipGetLastError());
   return VRT_OK;
 }
@@ -153,18 +160,42 @@ int vrt_render_ids(vrt_ctx* ctx, const vrt_camera* cam, const vrt_params* p, vrt
   VRT_HIP(ctx, hipSetDevice(s.device));
   const size_t px = size_t(cam->width) * size_t(cam->height);
   // the staging: synchronous calls only, so no launch still writes buffers that are replaced here
-  if (ctx->d_ids_stage.cap < px && !stage_alloc_all(px, ctx->d_ids_stage, ctx->d_depth_stage))
-    return fail(ctx, VRT_ERR_OOM, "hipMalloc ID pass staging");
+  if (ctx->d_ids_stage.cap < px) {
+    if (!stage_alloc_all(px, ctx->d_ids_stage, ctx->d_depth_stage) || !ctx->d_ids_count.alloc(1)) {
+      ctx->d_ids_stage.release();
+      ctx->d_depth_stage.release();
+      return fail(ctx, VRT_ERR_OOM, "hipMalloc ID pass staging");
+    }
+  }
   hipStream_t qs = main_stream(s);
-  st = enqueue_ids(ctx, cam, p, 0, cam->height, cam->width, ctx->d_ids_stage.p, depth ? ctx->d_depth_stage.p : nullptr, qs);
+  // the certified kernel counts its exact-path pixels into the context's word, zeroed here on the same stream;
+  // the exact kernel (mode 0, or the single layout) takes every pixel and needs no counter
+  const bool cert = ids_certified(ctx);
+  uint32_t n_exact = 0;
+  if (cert) VRT_HIP(ctx, hipMemsetAsync(ctx->d_ids_count.p, 0, sizeof(uint32_t), qs));
+  st = enqueue_ids(ctx, cam, p, 0, cam->height, cam->width, ctx->d_ids_stage.p, depth ? ctx->d_depth_stage.p : nullptr, qs,
+                   cert ? ctx->d_ids_count.p : nullptr);
   if (st != VRT_OK) return st;
   VRT_HIP(ctx, hipMemcpyAsync(ids, ctx->d_ids_stage.p, px * sizeof(vrt_pixel_id), hipMemcpyDeviceToHost, qs));
   if (depth) VRT_HIP(ctx, hipMemcpyAsync(depth, ctx->d_depth_stage.p, px * sizeof(float), hipMemcpyDeviceToHost, qs));
+  if (cert) VRT_HIP(ctx, hipMemcpyAsync(&n_exact, ctx->d_ids_count.p, sizeof(uint32_t), hipMemcpyDeviceToHost, qs));
   VRT_HIP(ctx, hipStreamSynchronize(qs));
-  // no certified ID kernel yet: every pixel takes the exact kernel, on every layout
   ctx->ids_pixels = px;
-  ctx->ids_deferred = px;
+  ctx->ids_deferred = cert ? n_exact : px;
   return VRT_OK;
+}
+
+int vrt_set_ids_certified(vrt_ctx* ctx, int32_t mode) {
+  if (!ctx) return VRT_ERR_INVALID;
+  if (mode != 0 && mode != 1) return fail(ctx, VRT_ERR_INVALID, "certified ID mode must be 0 or 1");
+  ctx->ids_cert_req = mode;
+  ctx->err.clear();
+  return VRT_OK;
+}
+
+int vrt_ids_certified(const vrt_ctx* ctx) {
+  if (!ctx) return VRT_ERR_INVALID;
+  return ids_certified(ctx) ? 1 : 0;
 }
 
 int vrt_ids_deferred(vrt_ctx* ctx, uint64_t* pixels, uint64_t* deferred) {

@@ -853,7 +853,7 @@ __global__ void __launch_bounds__(64, exact_cap_waves(kExactVgprs))
 #include "vrt_cert_debug_kernels.h"
 // the shaded ray-query kernels (vrt_trace_rays*, vrt_trace_pixels): after exact_pixel, which they call
 #include "vrt_trace_kernels.h"
-// the ID and depth pass (vrt_render_ids*): after primary_ray and the ray-query kernel's ray_hit_face
+// the ID and depth pass (vrt_render_ids*): after primary_ray, the ray-query kernel's ray_hit_face and vrt_cert.h
 #include "vrt_ids_kernels.h"
 // the reprojected temporal filter (vrt_reproject_temporal_async): after temporal_blend and primary_ray
 #include "vrt_reproject_kernels.h"
@@ -967,9 +967,13 @@ void launch_ray_trace(const KArgs& a, int32_t kind, const uint16_t* vox, const v
 }
 
 void launch_render_ids(const KArgs& a, const uint16_t* vox, vrt_pixel_id* ids, float* depth, hipStream_t s,
-                       hipEvent_t ev_begin, hipEvent_t ev_end) {
+                       hipEvent_t ev_begin, hipEvent_t ev_end, bool certified, uint32_t* n_exact) {
   const dim3 grid(uint32_t(a.width + 7) / 8u, uint32_t(a.rows + 7) / 8u);
-  launch_kernel(ids_exact_kernel, grid, dim3(64), 0, s, ev_begin, ev_end, a, vox, reinterpret_cast<uint2*>(ids), depth);
+  if (certified)
+    launch_kernel(ids_cert_kernel, grid, dim3(64), 0, s, ev_begin, ev_end, a, vox, reinterpret_cast<uint2*>(ids), depth,
+                  n_exact);
+  else
+    launch_kernel(ids_exact_kernel, grid, dim3(64), 0, s, ev_begin, ev_end, a, vox, reinterpret_cast<uint2*>(ids), depth);
 }
 
 void launch_reproject(const KArgs& a, const ReprojArgs& r, int32_t fetch, uint8_t* taps, hipStream_t s,
